@@ -16,7 +16,11 @@ One step = zero_grad -> forward -> loss -> backward (-> gradient all-reduce over
     python bench.py --gpus 1 --steps 20 --warmup 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times `--steps` steps and prints the headline
+(`value`, `ms_per_step`, ...).  `--dump-outputs DIR` writes what the last timed step produced (loss, a fixed seeded
+sample of the updated parameters and of the gradients, the float buffers such as BatchNorm running statistics) as
+DIR/<name>.npy in float32, so that two builds can be compared output for output.  `--full` adds, after the timed
+region, the legs below and `host_enqueue_ms_per_step` (three single steps into an empty queue):
   roofline     : the dominant kernel family (bf16 MFMA GEMM / implicit-GEMM conv core, csrc/gemm_core.h): algorithmic
                  FLOPs of its launches / their summed HIP-event durations, measured live in two extra instrumented steps
                  after the timed region (events perturb timing, so they are not in `value`); `by_class` splits the family
@@ -186,6 +190,33 @@ def roofline_by_class(path, steps):
     return out
 
 
+DUMP_SAMPLE = 1 << 22    # elements kept of a longer output (16 MiB in float32): the three sampled arrays stay below 64 MB
+
+
+def dump_outputs(net, loss, out_dir):
+    """What the last timed step hands its caller: the loss and the model state it updated -- parameters after the
+    optimizer step, their gradients (None -> zeros) and the float buffers (BatchNorm running statistics), each flattened
+    in named order.  An array longer than DUMP_SAMPLE is reduced to a fixed, seeded sample of (sorted, distinct) positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in net.named_parameters()]
+    arrays = {
+        "loss": loss.detach().float().reshape(1),
+        "params_sample": torch.cat([p.detach().reshape(-1).float() for p in params]),
+        "grads_sample": torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad).detach().reshape(-1).float()
+                                   for p in params]),
+    }
+    bufs = [b.detach().reshape(-1).float() for _, b in net.named_buffers() if b.is_floating_point()]
+    if bufs:
+        arrays["buffers_sample"] = torch.cat(bufs)
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).unique()
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(sorted(arrays))}")
+
+
 def gpu_leg(args, rank, world, local_rank):
     import hamspine
     from hamspine import _lib as L
@@ -232,6 +263,12 @@ def gpu_leg(args, rank, world, local_rank):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = tmax.item()
     final_loss = loss.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(net, loss, args.dump_outputs)
+    if not args.full:
+        log(f"rank {rank}: {args.steps} steps in {dt:.3f} s -> {dt / args.steps * 1e3:.2f} ms/step "
+            f"(host enqueue: {t_issue / args.steps * 1e3:.2f} ms/step inside the timed loop), loss {final_loss:.4f}")
+        return dt, final_loss, nparams, {}
     # host cost of enqueuing ONE step into an empty queue (in the timed loop above the host runs at most a queue's depth
     # ahead of the GPU and then blocks inside the launch call, so its per-step time there only mirrors the GPU's)
     host_samples = []
@@ -359,7 +396,12 @@ def gpu_leg(args, rank, world, local_rank):
         except Exception as e:      # noqa: BLE001  (reported in the line, never fatal for the headline)
             ddp_cfg = {"error": repr(e)}
             log(f"ddp-config leg failed: {e!r}")
-    return dt, final_loss, roofline, nparams, host_ms, f32_mode, ddp_cfg
+    extra = {"host_enqueue_ms_per_step": round(host_ms, 3), "roofline": roofline}
+    if f32_mode is not None:
+        extra["f32_mode"] = f32_mode
+    if ddp_cfg is not None:
+        extra["ddp_config"] = ddp_cfg
+    return dt, final_loss, nparams, extra
 
 
 def ddp_config_leg(net, fwd_loss, make_opt, device, batch, steps):
@@ -474,11 +516,17 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2")
     ap.add_argument("--seq-len", type=int, default=128, help="caption length (the reference's MIBF loader pads to 256, "
                     "mibf_net/dataset_spine.py:88; the metric of BASELINE.json is quoted at 128)")
-    ap.add_argument("--gemm-log", default=None, help="copy the per-launch CSV of the roofline leg to this file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="after the headline, run the host-enqueue probe and the roofline, "
+                    "f32-mode, data-parallel-configuration and CPU-baseline legs")
+    ap.add_argument("--gemm-log", default=None, help="copy the per-launch CSV of the roofline leg to this file (needs --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-f32", action="store_true", help="skip the exact-f32 mode leg")
     ap.add_argument("--no-ddp-config", action="store_true", help="skip the N=1 leg that runs the data-parallel configuration")
     args = ap.parse_args()
+    if args.gemm_log and not args.full:
+        ap.error("--gemm-log records the roofline leg, which runs only with --full")
     global SEQ
     SEQ = args.seq_len
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -511,7 +559,7 @@ def main():
     from hamspine import _lib as _L
     if _L.lib().hs_measure_build() and os.environ.get("HAMSPINE_ALLOW_MEASURE_BUILD") != "1":
         sys.exit("bench.py: libhamspine_hip.so was built with -DHS_MEASURE (knockout switches compiled in); rebuild without it")
-    dt, final_loss, roofline, nparams, host_ms, f32_mode, ddp_cfg = gpu_leg(args, rank, world, local_rank)
+    dt, final_loss, nparams, extra = gpu_leg(args, rank, world, local_rank)
     if rank == 0:
         value = batch * world * args.steps / dt
         ms_step = dt / args.steps * 1e3
@@ -527,15 +575,10 @@ def main():
             "config": {"workload": desc, "per_gpu_batch": batch, "global_batch": batch * world,
                        "seq_len": SEQ, "params": nparams, "parallelism": f"dp{world}"},
             "step_mfma_frac": round(train_tflop / (ms_step * 1e-3) / MFMA_BF16_PEAK_TFLOPS, 4),
-            "host_enqueue_ms_per_step": round(host_ms, 3),
             "final_loss": round(final_loss, 4),
-            "roofline": roofline,
+            **extra,
         }
-        if f32_mode is not None:
-            out["f32_mode"] = f32_mode
-        if ddp_cfg is not None:
-            out["ddp_config"] = ddp_cfg
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("timing the CPU oracle (bounded sample) ...")
             out["cpu_baseline"] = cpu_leg(args.workload)
         print(json.dumps(out), flush=True)
