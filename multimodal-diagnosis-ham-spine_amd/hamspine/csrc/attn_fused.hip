@@ -1,4 +1,5 @@
-// Fused attention (bf16; head dim 64 or 32; any number of queries in 128-row chunks; Lk <= 128 keys).  Forward, BERT shape
+// Fused attention (bf16; head dim 64 or 32; any number of queries in 128-row chunks; Lk <= 128 keys, and at head dim 64
+// up to 512 keys: 64-row chunks beyond 256 keys forward, key blocks of 128 backward).  Forward, BERT shape
 // first: one workgroup per (batch, head[, query chunk]) keeps
 // Q, K, V in LDS (48 KiB) and the 128x128 score tile in registers:
 //     S = scale * Q K^T (+ key mask)  ->  P = softmax(S)  ->  Pd = dropout(P)  ->  O = Pd V
@@ -48,15 +49,17 @@ struct AttnFusedArgs {
 // 107-113).  blockIdx.y = query chunk: rows [128 y, 128 y + 128) of the Lq queries (the 784 x 128 score tile of the layer-2
 // CrossAttentionBlock is 7 chunks); every chunk stages all Lk <= 128 keys.
 // LK: key capacity of the workgroup (128, or 256: BERT at the MIBF loader's caption padding of 256 tokens -- 80 KiB of LDS, the
-// 128 x 256 score tile is 128 accumulator registers per lane)
-template <int HD, int LK = 128>
+// 128 x 256 score tile is 128 accumulator registers per lane; or 512: the ConNeXT loader's longest captions, with FM = 1)
+// FM: 16-row query fragments per wave; the chunk is 64 * FM queries.  FM = 1 at LK = 512 keeps the 64 x 512 score tile at
+// the same 128 registers per lane; K and V for 512 keys take 2 x 64 KiB of LDS, 136 KiB with Q (one workgroup per CU)
+template <int HD, int LK = 128, int FM = 2>
 __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs a) {
-    constexpr int LMAX = 128, CPR = HD / 8, NP = LMAX * HD * 2 / 1024 / 4;      // DMA pieces per wave per tile (queries)
+    constexpr int LMAX = 64 * FM, CPR = HD / 8, NP = LMAX * HD * 2 / 1024 / 4;  // DMA pieces per wave per tile (queries)
     constexpr int NPK = LK * HD * 2 / 1024 / 4;                                 // ... of the key / value tiles
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef __attribute__((address_space(3))) char lds_char;
-    char* Qs = smem;                    // [128 queries][64]  k-contiguous, XOR swizzled (kc_off_bf16<64>)
-    char* Ks = smem + LMAX * HD * 2;    // [128 keys][64]     k-contiguous
+    char* Qs = smem;                    // [LMAX queries][64] k-contiguous, XOR swizzled (kc_off_bf16<64>)
+    char* Ks = smem + LMAX * HD * 2;    // [LK keys][64]      k-contiguous
     char* Vs = smem + (LMAX + LK) * HD * 2;  // [LK keys][64]   key-major ("row-contiguous") for the P V product
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -99,8 +102,8 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    // ---- S = Q K^T: this wave owns query rows [32 wave, 32 wave + 32) ---------------------------------------------
-    constexpr int FM = 2, FN = LK / 16;
+    // ---- S = Q K^T: this wave owns query rows [16 FM wave, 16 FM wave + 16 FM) -------------------------------------
+    constexpr int FN = LK / 16;
     f32x4 acc[FM][FN];
 #pragma unroll
     for (int i = 0; i < FM; ++i)
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
     for (int ks = 0; ks < HD / 32; ++ks) {
         bf16x8 af[FM], bf[FN];
 #pragma unroll
-        for (int i = 0; i < FM; ++i) af[i] = *(const bf16x8*)(Qs + kc_off_bf16<HD>(wave * 32 + i * 16 + l15, ks * 4 + g));
+        for (int i = 0; i < FM; ++i) af[i] = *(const bf16x8*)(Qs + kc_off_bf16<HD>(wave * 16 * FM + i * 16 + l15, ks * 4 + g));
 #pragma unroll
         for (int j = 0; j < FN; ++j) bf[j] = *(const bf16x8*)(Ks + kc_off_bf16<HD>(j * 16 + l15, ks * 4 + g));
 #pragma unroll
@@ -119,7 +122,7 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
             for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j], af[i], acc[i][j], 0, 0, 0);
     }
 
-    // ---- softmax over the 128 keys of each row; lane holds keys 16 j + 4 g + e of row 32 wave + 16 i + l15 --------
+    // ---- softmax over the LK keys of each row; lane holds keys 16 j + 4 g + e of row 16 FM wave + 16 i + l15 ------
     const long long* mk = a.key_mask ? a.key_mask + (long long)b * a.Lk : nullptr;
     bool dead[FN][4];
 #pragma unroll
@@ -131,7 +134,7 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
         }
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
-        const int qrow = q0 + wave * 32 + i * 16 + l15;
+        const int qrow = q0 + wave * 16 * FM + i * 16 + l15;
         float mx = -INFINITY;
 #pragma unroll
         for (int j = 0; j < FN; ++j)
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
     }
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
-        const int qrow = q0 + wave * 32 + i * 16 + l15;
+        const int qrow = q0 + wave * 16 * FM + i * 16 + l15;
         if (qrow >= a.Lq) continue;
         bf16_t* orow = (bf16_t*)a.o + (long long)b * a.o_bs + (long long)qrow * a.o_ld + (long long)h * HD;
 #pragma unroll
@@ -699,6 +702,309 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_gen_kernel(const AttnFused
     store_keys(tk, a.dk, a.k_bs, a.k_ld, a.scale);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Long backward: head dim 64, any number of queries, 129..512 keys in blocks of 128.  One workgroup per (batch, head):
+//   0. delta[q] = sum over ALL keys of P * dP (dP = dPd * M), the one term of the softmax backward that spans the key
+//      blocks, one f32 per row to scratch.  It equals rowsum(dO o O) with O = Pd V: from O when the caller has it (the
+//      BERT layer keeps it as the out-projection input), else dO V^T per (query chunk, key block) summed over the blocks
+//   then, key block outer and query chunk inner, phases A-D of the general kernel with delta in place of the in-tile row
+//   dot.  dK / dV of a key block are summed over the chunks in registers; dQ is summed over the key blocks through an
+//   f32 slab [B*H][Lq][64] that only this workgroup reads and writes, in key-block order: no atomics, bitwise repeatable.
+// LDS as the general kernel: 112 KiB, one workgroup per CU.
+// ------------------------------------------------------------------------------------------------------------------
+struct AttnFusedBwdLongArgs {
+    AttnFusedBwdArgs a;
+    const char* O;                    // forward output, strides of dO; NULL: delta from a sweep over the key blocks
+    float* dq_acc;                    // [B*H][Lq][64] f32 scratch
+    float* delta;                     // [B*H][Lq]     f32 scratch
+};
+
+__global__ __launch_bounds__(256) void attn_bwd_fused_long_kernel(const AttnFusedBwdLongArgs la) {
+    const AttnFusedBwdArgs& a = la.a;
+    constexpr int HD = 64, LMAX = 128, CPR = HD / 8, TILE = LMAX * HD * 2, NP = TILE / 1024 / 4;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    typedef __attribute__((address_space(3))) char lds_char;
+    char* Vkc = smem;                // V block  [key][hd] k-contiguous
+    char* Okc = smem + TILE;         // dO chunk [q][hd]   k-contiguous
+    char* Orc = smem + 2 * TILE;     // dO chunk [q][hd]   key-major
+    char* Krc = smem + 3 * TILE;     // K block  [key][hd] key-major
+    char* Qrc = smem + 4 * TILE;     // Q chunk  [q][hd]   key-major
+    char* PS = smem + 5 * TILE;      // [q][key] bf16 transpose tile (32 KiB): Pd, then dS
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, l15 = lane & 15;
+    const int bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
+    const long long qo = (long long)b * a.q_bs + (long long)h * HD, ko = (long long)b * a.k_bs + (long long)h * HD;
+    const long long vo = (long long)b * a.v_bs + (long long)h * HD, oo = (long long)b * a.o_bs + (long long)h * HD;
+    const __amdgpu_buffer_rsrc_t rq = make_rsrc(a.q + qo * 2, (unsigned)min(a.q_bytes - (unsigned long long)qo * 2, 0x7fffff00ull));
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.k + ko * 2, (unsigned)min(a.k_bytes - (unsigned long long)ko * 2, 0x7fffff00ull));
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.v + vo * 2, (unsigned)min(a.v_bytes - (unsigned long long)vo * 2, 0x7fffff00ull));
+    const __amdgpu_buffer_rsrc_t ro = make_rsrc(a.dO + oo * 2, (unsigned)min(a.o_bytes - (unsigned long long)oo * 2, 0x7fffff00ull));
+    float* dq_acc = la.dq_acc + (long long)bh * a.Lq * HD;
+    float* delta = la.delta + (long long)bh * a.Lq;
+
+    // LDS-DMA staging of 128 rows [r0, r0 + 128) of a [L][ld] operand (rows >= L read as zero)
+    auto stage_kc = [&](const __amdgpu_buffer_rsrc_t& rs, char* dst, int r0, int L, int ld) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int s = (wave * NP + i) * 64 + lane;
+            const int r = s / CPR, pc = s % CPR;
+            const int kl = (pc ^ kc_swz<CPR>(r)) * 8;
+            const unsigned off = r0 + r < L ? (unsigned)(((r0 + r) * ld + kl) * 2) : kOOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)((lds_char*)dst + (wave * NP + i) * 1024), 16, off, 0, 0, 0);
+        }
+    };
+    auto stage_rc = [&](const __amdgpu_buffer_rsrc_t& rs, char* dst, int r0, int L, int ld) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int s = (wave * NP + i) * 64 + lane;
+            const int row = s / (HD / 8), pcc = s % (HD / 8);
+            const int col = rc_logical_chunk<HD>(row, pcc) * 8;
+            const unsigned off = r0 + row < L ? (unsigned)(((r0 + row) * ld + col) * 2) : kOOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)((lds_char*)dst + (wave * NP + i) * 1024), 16, off, 0, 0, 0);
+        }
+    };
+    constexpr int FM = 2, FN = 8, FO = HD / 16;
+    // dPd = dO V^T for this wave's 32 query rows of the staged chunk against the staged key block
+    auto dov = [&](f32x4 (&acc)[FM][FN]) {
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+            for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < HD / 32; ++ks) {
+            bf16x8 af[FM], bf[FN];
+#pragma unroll
+            for (int i = 0; i < FM; ++i) af[i] = *(const bf16x8*)(Okc + kc_off_bf16<HD>(wave * 32 + i * 16 + l15, ks * 4 + g));
+#pragma unroll
+            for (int j = 0; j < FN; ++j) bf[j] = *(const bf16x8*)(Vkc + kc_off_bf16<HD>(j * 16 + l15, ks * 4 + g));
+#pragma unroll
+            for (int i = 0; i < FM; ++i)
+#pragma unroll
+                for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j], af[i], acc[i][j], 0, 0, 0);
+        }
+    };
+    // P of 4 keys from HBM and the regenerated keep-scales (keys past ldP / rows past Lq read as 0)
+    auto load_p = [&](int qrow, long long prow, int key0, float (&pv)[4], float (&sc)[4]) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { pv[e] = 0.f; sc[e] = 1.f; }
+        if (qrow < a.Lq && key0 < a.ldP) {
+            const u32x2 raw = *(const u32x2*)((const bf16_t*)a.P + prow * a.ldP + key0);
+            pv[0] = __uint_as_float(raw[0] << 16); pv[1] = __uint_as_float(raw[0] & 0xffff0000u);
+            pv[2] = __uint_as_float(raw[1] << 16); pv[3] = __uint_as_float(raw[1] & 0xffff0000u);
+        }
+        if (a.thresh && key0 < a.Lk) attn_drop4(a.seed, (unsigned long long)prow * a.Lk + key0, a.thresh, a.inv_keep, sc);
+    };
+
+    const int nchunks = (a.Lq + LMAX - 1) / LMAX, nkb = (a.Lk + LMAX - 1) / LMAX;
+
+    // ---- 0. delta per query row ------------------------------------------------------------------------------------
+    if (la.O) {
+        // rowsum(dO o O): the 4 lanes of a row (g) take 16 head columns each
+        for (int r0 = wave * 16; r0 < a.Lq; r0 += 64) {
+            const int qrow = r0 + l15;
+            float d = 0.f;
+            if (qrow < a.Lq) {
+                const long long off = (long long)b * a.o_bs + (long long)qrow * a.o_ld + (long long)h * HD + g * 16;
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh) {
+                    const u32x4 x = *(const u32x4*)((const bf16_t*)a.dO + off + hh * 8);
+                    const u32x4 y = *(const u32x4*)((const bf16_t*)la.O + off + hh * 8);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        d = fmaf(__uint_as_float(x[e] << 16), __uint_as_float(y[e] << 16), d);
+                        d = fmaf(__uint_as_float(x[e] & 0xffff0000u), __uint_as_float(y[e] & 0xffff0000u), d);
+                    }
+                }
+            }
+            d += __shfl_xor(d, 16, 64);
+            d += __shfl_xor(d, 32, 64);
+            if (g == 0 && qrow < a.Lq) delta[qrow] = d;
+        }
+    } else for (int c = 0; c < nchunks; ++c) {
+        const int q0 = c * LMAX;
+        float dot[FM] = {0.f, 0.f};
+        for (int kb = 0; kb < nkb; ++kb) {
+            const int k0 = kb * LMAX;
+            if (kb == 0) stage_kc(ro, Okc, q0, a.Lq, a.o_ld);
+            stage_kc(rv, Vkc, k0, a.Lk, a.v_ld);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            f32x4 acc[FM][FN];
+            dov(acc);
+#pragma unroll
+            for (int i = 0; i < FM; ++i) {
+                const int qrow = q0 + wave * 32 + i * 16 + l15;
+                const long long prow = (long long)bh * a.Lq + qrow;
+#pragma unroll
+                for (int j = 0; j < FN; ++j) {
+                    float pv[4], sc[4];
+                    load_p(qrow, prow, k0 + j * 16 + 4 * g, pv, sc);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dot[i] = fmaf(acc[i][j][e] * sc[e], pv[e], dot[i]);
+                }
+            }
+            __syncthreads();                               // the V block (and at the last block the dO chunk) may be restaged
+        }
+#pragma unroll
+        for (int i = 0; i < FM; ++i) {
+            float d = dot[i];
+            d += __shfl_xor(d, 16, 64);
+            d += __shfl_xor(d, 32, 64);
+            const int qrow = q0 + wave * 32 + i * 16 + l15;
+            if (g == 0 && qrow < a.Lq) delta[qrow] = d;
+        }
+    }
+    __syncthreads();                                       // delta rows are visible to the whole workgroup
+
+    // ---- per key block: dK / dV summed over the query chunks; dQ summed over the key blocks in the slab -------------
+    for (int kb = 0; kb < nkb; ++kb) {
+        const int k0 = kb * LMAX;
+        stage_kc(rv, Vkc, k0, a.Lk, a.v_ld);
+        stage_rc(rk, Krc, k0, a.Lk, a.k_ld);
+        f32x4 tv[FM][FO], tk[FM][FO];
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+            for (int jn = 0; jn < FO; ++jn) {
+                tv[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+                tk[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        for (int c = 0; c < nchunks; ++c) {
+            const int q0 = c * LMAX;
+            stage_kc(ro, Okc, q0, a.Lq, a.o_ld);
+            stage_rc(ro, Orc, q0, a.Lq, a.o_ld);
+            stage_rc(rq, Qrc, q0, a.Lq, a.q_ld);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+
+            // ---- A. dPd = dO V^T, then dS = P * (dPd * M - delta); Pd to the transpose tile, dS stays in acc
+            f32x4 acc[FM][FN];
+            dov(acc);
+#pragma unroll
+            for (int i = 0; i < FM; ++i) {
+                const int lrow = wave * 32 + i * 16 + l15, qrow = q0 + lrow;
+                const long long prow = (long long)bh * a.Lq + qrow;
+                const float dl = qrow < a.Lq ? delta[qrow] : 0.f;
+#pragma unroll
+                for (int j = 0; j < FN; ++j) {
+                    float pv[4], sc[4], pd[4];
+                    load_p(qrow, prow, k0 + j * 16 + 4 * g, pv, sc);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        pd[e] = pv[e] * sc[e];
+                        acc[i][j][e] = pv[e] * (acc[i][j][e] * sc[e] - dl);
+                    }
+                    *(bf16x4*)(PS + rc_off_bf16<LMAX>(lrow, j * 16 + 4 * g)) = bf16x4{(bf16_t)pd[0], (bf16_t)pd[1], (bf16_t)pd[2], (bf16_t)pd[3]};
+                }
+            }
+            // ---- B. dQ += scale * dS K over this key block: slab read-modify-write in key-block order
+            {
+                f32x4 qa[FM][FO];
+#pragma unroll
+                for (int i = 0; i < FM; ++i)
+#pragma unroll
+                    for (int jn = 0; jn < FO; ++jn) qa[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kk = 0; kk < LMAX / 32; ++kk) {
+                    bf16x8 sa[FM], kbf[FO];
+#pragma unroll
+                    for (int i = 0; i < FM; ++i) {
+                        const f32x4 lo = acc[i][2 * kk], hi = acc[i][2 * kk + 1];
+                        sa[i] = bf16x8{(bf16_t)lo[0], (bf16_t)lo[1], (bf16_t)lo[2], (bf16_t)lo[3],
+                                       (bf16_t)hi[0], (bf16_t)hi[1], (bf16_t)hi[2], (bf16_t)hi[3]};
+                    }
+#pragma unroll
+                    for (int jn = 0; jn < FO; ++jn) {
+                        const int col = jn * 16 + 4 * (lane & 3);
+                        const int k_lo = kk * 32 + 4 * g + (l15 >> 2), k_hi = k_lo + 16;
+                        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(Krc + rc_off_bf16<HD>(k_lo, col)));
+                        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(Krc + rc_off_bf16<HD>(k_hi, col)));
+                        kbf[jn] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                    }
+#pragma unroll
+                    for (int i = 0; i < FM; ++i)
+#pragma unroll
+                        for (int jn = 0; jn < FO; ++jn) qa[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kbf[jn], sa[i], qa[i][jn], 0, 0, 0);
+                }
+#pragma unroll
+                for (int i = 0; i < FM; ++i) {
+                    const int qrow = q0 + wave * 32 + i * 16 + l15;
+                    if (qrow >= a.Lq) continue;
+                    float* srow = dq_acc + (long long)qrow * HD;
+                    bf16_t* row = (bf16_t*)a.dq + (long long)b * a.q_bs + (long long)qrow * a.q_ld + (long long)h * HD;
+#pragma unroll
+                    for (int jn = 0; jn < FO; ++jn) {
+                        f32x4 v = qa[i][jn];
+                        if (kb > 0) v += *(const f32x4*)(srow + jn * 16 + 4 * g);      // this lane's own partial sum
+                        if (kb + 1 < nkb) *(f32x4*)(srow + jn * 16 + 4 * g) = v;
+                        else *(bf16x4*)(row + jn * 16 + 4 * g) = bf16x4{(bf16_t)(v[0] * a.scale), (bf16_t)(v[1] * a.scale),
+                                                                        (bf16_t)(v[2] * a.scale), (bf16_t)(v[3] * a.scale)};
+                    }
+                }
+            }
+            // ---- C / D. transposed products over the chunk's 128 query rows, accumulated into this wave's 32 keys
+            auto transposed_accumulate = [&](const char* rhs_rc, f32x4 (&ta)[FM][FO]) {
+#pragma unroll
+                for (int ks = 0; ks < LMAX / 32; ++ks) {
+                    bf16x8 pa[FM], rb[FO];
+                    const int kr = ks * 32 + 8 * g + (l15 >> 2);
+#pragma unroll
+                    for (int i = 0; i < FM; ++i) {
+                        const int col = wave * 32 + i * 16 + 4 * (lane & 3);
+                        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(PS + rc_off_bf16<LMAX>(kr, col)));
+                        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(PS + rc_off_bf16<LMAX>(kr + 4, col)));
+                        pa[i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                    }
+#pragma unroll
+                    for (int jn = 0; jn < FO; ++jn) {
+                        const int col = jn * 16 + 4 * (lane & 3);
+                        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(rhs_rc + rc_off_bf16<HD>(kr, col)));
+                        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(rhs_rc + rc_off_bf16<HD>(kr + 4, col)));
+                        rb[jn] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                    }
+#pragma unroll
+                    for (int i = 0; i < FM; ++i)
+#pragma unroll
+                        for (int jn = 0; jn < FO; ++jn) ta[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb[jn], pa[i], ta[i][jn], 0, 0, 0);
+                }
+            };
+            __syncthreads();                               // every wave's Pd rows are in the transpose tile
+            transposed_accumulate(Orc, tv);                // dV += Pd^T dO
+            __syncthreads();                               // all reads of Pd done
+#pragma unroll
+            for (int i = 0; i < FM; ++i) {
+                const int lrow = wave * 32 + i * 16 + l15;
+#pragma unroll
+                for (int j = 0; j < FN; ++j) {
+                    const f32x4 v = acc[i][j];
+                    *(bf16x4*)(PS + rc_off_bf16<LMAX>(lrow, j * 16 + 4 * g)) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+                }
+            }
+            __syncthreads();
+            transposed_accumulate(Qrc, tk);                // dK += dS^T Q   (scaled at the store)
+            __syncthreads();                               // the chunk's tiles (and after the last chunk the block's) may be restaged
+        }
+        auto store_keys = [&](const f32x4 (&ta)[FM][FO], char* out, long long out_bs, int out_ld, float alpha) {
+#pragma unroll
+            for (int i = 0; i < FM; ++i) {
+                const int key = k0 + wave * 32 + i * 16 + l15;
+                if (key >= a.Lk) continue;
+                bf16_t* row = (bf16_t*)out + (long long)b * out_bs + (long long)key * out_ld + (long long)h * HD;
+#pragma unroll
+                for (int jn = 0; jn < FO; ++jn) {
+                    const f32x4 v = ta[i][jn];
+                    *(bf16x4*)(row + jn * 16 + 4 * g) = bf16x4{(bf16_t)(v[0] * alpha), (bf16_t)(v[1] * alpha), (bf16_t)(v[2] * alpha),
+                                                               (bf16_t)(v[3] * alpha)};
+                }
+            }
+        };
+        store_keys(tv, a.dv, a.v_bs, a.v_ld, 1.f);
+        store_keys(tk, a.dk, a.k_bs, a.k_ld, a.scale);
+    }
+}
+
 // host side: eligibility + launch.  Returns 1 when the fused kernel ran, 0 when the shape is not covered, < 0 on error.
 int attention_fwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, void* o, void* P, void* Pd,
                         int ldP, hipStream_t s) {
@@ -708,9 +1014,9 @@ int attention_fwd_fused(const hs_attn_desc& d, const void* q, const void* k, con
         enabled = (e && e[0] == '0') ? 0 : 1;
     }
     // head dim 64 (BERT) or 32 (the fusion modules' 8-head attention over 256 features), any number of queries (128-row
-    // chunks on grid.y), at most 128 keys -- 256 at head dim 64, forward only: the backward of such a call takes the unfused
-    // kernels on the probabilities this kernel stored
-    if (!enabled || d.dtype != HS_BF16 || (d.hd != 64 && d.hd != 32) || d.Lq < 1 || d.Lq > 128 * 65535 || d.Lk < 1 || d.Lk > (d.hd == 64 ? 256 : 128) || ldP % 4 != 0 || ldP < d.Lk) return 0;
+    // chunks on grid.y), at most 128 keys -- 512 at head dim 64 (257..512 keys: 64-row chunks)
+    const bool wide = d.hd == 64 && d.Lk > 256;
+    if (!enabled || d.dtype != HS_BF16 || (d.hd != 64 && d.hd != 32) || d.Lq < 1 || d.Lq > (wide ? 64 : 128) * 65535 || d.Lk < 1 || d.Lk > (d.hd == 64 ? 512 : 128) || ldP % 4 != 0 || ldP < d.Lk) return 0;
     const long long strides[] = {d.q_bs, d.k_bs, d.v_bs, d.o_bs, d.q_ld, d.k_ld, d.v_ld, d.o_ld};
     for (long long x : strides)
         if (x % 8 != 0) return 0;
@@ -741,24 +1047,31 @@ int attention_fwd_fused(const hs_attn_desc& d, const void* q, const void* k, con
         if (hipFuncSetAttribute((const void*)attn_fwd_fused_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 128 * 64 * 2) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)attn_fwd_fused_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 128 * 32 * 2) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)attn_fwd_fused_kernel<64, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (128 + 2 * 256) * 64 * 2) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)attn_fwd_fused_kernel<64, 512, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (64 + 2 * 512) * 64 * 2) != hipSuccess) return -1;
         attr_set = true;
     }
     const dim3 grid(d.B * d.H, (d.Lq + 127) / 128);
-    if (d.hd == 64 && d.Lk > 128) hipLaunchKernelGGL((attn_fwd_fused_kernel<64, 256>), grid, dim3(256), (128 + 2 * 256) * 64 * 2, s, a);
+    if (wide) hipLaunchKernelGGL((attn_fwd_fused_kernel<64, 512, 1>), dim3(d.B * d.H, (d.Lq + 63) / 64), dim3(256), (64 + 2 * 512) * 64 * 2, s, a);
+    else if (d.hd == 64 && d.Lk > 128) hipLaunchKernelGGL((attn_fwd_fused_kernel<64, 256>), grid, dim3(256), (128 + 2 * 256) * 64 * 2, s, a);
     else if (d.hd == 64) hipLaunchKernelGGL(attn_fwd_fused_kernel<64>, grid, dim3(256), 3 * 128 * 64 * 2, s, a);
     else hipLaunchKernelGGL(attn_fwd_fused_kernel<32>, grid, dim3(256), 3 * 128 * 32 * 2, s, a);
     if (hipGetLastError() != hipSuccess) return -1;
     return 1;
 }
 
+// scratch: f32 workspace of scratch_bytes, used beyond 128 keys for the dQ slab and the row terms (B*H*Lq*65 floats);
+// O: the forward output with dO's strides, or NULL (used beyond 128 keys only)
 int attention_bwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, const void* dO, void* dq, void* dk,
-                        void* dv, const void* P, int ldP, hipStream_t s) {
+                        void* dv, const void* P, int ldP, void* scratch, long long scratch_bytes, const void* O, hipStream_t s) {
     static int enabled = -1;
     if (enabled < 0) {
         const char* e = getenv("HAMSPINE_FUSED_ATTENTION");
         enabled = (e && e[0] == '0') ? 0 : 1;
     }
-    if (!enabled || d.dtype != HS_BF16 || (d.hd != 64 && d.hd != 32) || d.Lq < 1 || d.Lk < 1 || d.Lk > 128 || ldP % 4 != 0 || ldP < d.Lk) return 0;
+    if (!enabled || d.dtype != HS_BF16 || (d.hd != 64 && d.hd != 32) || d.Lq < 1 || d.Lk < 1 || d.Lk > (d.hd == 64 ? 512 : 128) || ldP % 4 != 0 || ldP < d.Lk) return 0;
+    const bool long_keys = d.Lk > 128;
+    const long long rows = (long long)d.B * d.H * d.Lq;
+    if (long_keys && (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < rows * (64 + 1) * 4)) return 0;
     const long long strides[] = {d.q_bs, d.k_bs, d.v_bs, d.o_bs, d.q_ld, d.k_ld, d.v_ld, d.o_ld};
     for (long long x : strides)
         if (x % 8 != 0) return 0;
@@ -790,10 +1103,19 @@ int attention_bwd_fused(const hs_attn_desc& d, const void* q, const void* k, con
         if (hipFuncSetAttribute((const void*)attn_bwd_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)attn_bwd_fused_gen_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g64) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)attn_bwd_fused_gen_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g32) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)attn_bwd_fused_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g64) != hipSuccess) return -1;
         attr_set = true;
     }
+    if (long_keys) {             // head dim 64, 129..512 keys: key blocks of 128, dQ summed through the scratch slab
+        AttnFusedBwdLongArgs la;
+        la.a = a;
+        la.O = ((uintptr_t)O & 15) ? nullptr : (const char*)O;
+        la.dq_acc = (float*)scratch;
+        la.delta = (float*)scratch + rows * 64;
+        hipLaunchKernelGGL(attn_bwd_fused_long_kernel, dim3(d.B * d.H), dim3(256), lds_g64, s, la);
+    }
     // the BERT shape keeps its own kernel (transpose tile aliased onto dead operand tiles: two workgroups per CU)
-    if (d.hd == 64 && d.Lq <= 128) hipLaunchKernelGGL(attn_bwd_fused_kernel, dim3(d.B * d.H), dim3(256), lds, s, a);
+    else if (d.hd == 64 && d.Lq <= 128) hipLaunchKernelGGL(attn_bwd_fused_kernel, dim3(d.B * d.H), dim3(256), lds, s, a);
     else if (d.hd == 64) hipLaunchKernelGGL(attn_bwd_fused_gen_kernel<64>, dim3(d.B * d.H), dim3(256), lds_g64, s, a);
     else hipLaunchKernelGGL(attn_bwd_fused_gen_kernel<32>, dim3(d.B * d.H), dim3(256), lds_g32, s, a);
     if (hipGetLastError() != hipSuccess) return -1;

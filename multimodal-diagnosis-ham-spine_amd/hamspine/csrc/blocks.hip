@@ -33,7 +33,7 @@ GemmGroup* gemm_group_open(hipStream_t s, long long slot);   // slot: any key th
 int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s);
 int gemm_group_flush(GemmGroup* g, hipStream_t s);
 int attention_bwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, const void* dO, void* dq, void* dk,
-                        void* dv, const void* P, int ldP, hipStream_t s);
+                        void* dv, const void* P, int ldP, void* scratch, long long scratch_bytes, const void* O, hipStream_t s);
 int attention_fwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, void* o, void* P, void* Pd, int ldP,
                         hipStream_t s);
 
@@ -338,8 +338,9 @@ static int attention_fwd_run(Run& r, const hs_attn_desc& d, const void* q, const
     return HS_OK;
 }
 
+// o: the forward output (same strides as dO) when the caller still holds it, else NULL
 static int attention_bwd_run(Run& r, const hs_attn_desc& d, const void* q, const void* k, const void* v, const void* dO,
-                             void* dq, void* dk, void* dv) {
+                             void* dq, void* dk, void* dv, const void* o = nullptr) {
     HS_PROPAGATE(attn_check(d));
     AttnLayout l = attn_layout(d, r, true);
     const int BH = d.B * d.H;
@@ -347,8 +348,9 @@ static int attention_bwd_run(Run& r, const hs_attn_desc& d, const void* q, const
     const long long p_el = (long long)BH * d.Lq * l.ldP;
     if (!r.plan && (knock() & 256)) return HS_OK;
     if (!r.plan && !r.saved.overflow && !r.ws.overflow) {
-        // BERT shape: one fused kernel (csrc/attn_fused.hip) instead of four batched GEMMs and the softmax backward
-        const int fused = attention_bwd_fused(d, q, k, v, dO, dq, dk, dv, l.P, l.ldP, r.s);
+        // BERT shape: one fused kernel (csrc/attn_fused.hip) instead of four batched GEMMs and the softmax backward; beyond
+        // 128 keys it keeps its f32 dQ slab in the dP buffer the unfused path would use
+        const int fused = attention_bwd_fused(d, q, k, v, dO, dq, dk, dv, l.P, l.ldP, l.S, (long long)BH * d.Lq * d.Lk * 4, o, r.s);
         if (fused < 0) {
             set_error("attention_bwd: fused kernel launch failed");
             return HS_ERR_HIP;
@@ -1540,7 +1542,7 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
     const char* qkv = (const char*)L.qkv;
     char* dq = (char*)dqkv;
     HS_PROPAGATE(attention_bwd_run(r, a, qkv, qkv ? qkv + (long long)Hd * es : nullptr, qkv ? qkv + 2ll * Hd * es : nullptr,
-                                   dctx, dq, dq ? dq + (long long)Hd * es : nullptr, dq ? dq + 2ll * Hd * es : nullptr));
+                                   dctx, dq, dq ? dq + (long long)Hd * es : nullptr, dq ? dq + 2ll * Hd * es : nullptr, L.ctx));
     // ---- QKV projection ----
     HS_PROPAGATE(on_side(r, [&]() -> int {
         // one GEMM for the three weight gradients: [dWq; dWk; dWv] = dqkv^T x, rows routed to the three tensors
