@@ -428,6 +428,51 @@ hs_status hs_gru_cell_fwd(const float* gx, int32_t ldx, const float* gh, int32_t
 hs_status hs_gru_cell_bwd(const float* dh, const float* act, const float* h_prev, float* dgx, float* dgh, float* dh_prev,
                           int32_t B, int32_t H, void* stream);
 
+/* ------------------------------------------------------------------------------------------- */
+/* Mamba block of the SSM fusion (reference modules/fusion_blocks.py:264-292 -> mamba_ssm.Mamba    */
+/* with d_state 16, d_conv 4).  Activations are HS_F32 / HS_BF16 matrices [B*L][d] with explicit   */
+/* row pitches (elements; each a multiple of 16 bytes and >= d), so slices of the in_proj / x_proj */
+/* outputs are read in place.  Parameters are f32.  State and every sum are f32; all reductions    */
+/* run in a fixed order (results repeat bitwise).  Unsupported arguments (N != 16, k != 4,         */
+/* misaligned pitches, empty shapes) return HS_ERR_UNSUPPORTED without a launch.                   */
+/* ------------------------------------------------------------------------------------------- */
+/* y[b][t][c] = silu(bias[c] + sum_j w[c][j] * x[b][t-3+j][c]), x = 0 before t = 0
+   (reference modules/fusion_blocks.py:264-292: Mamba.conv1d, depthwise, k = 4, left pad 3). */
+hs_status hs_causal_conv1d_fwd(int32_t dtype, const void* x, int32_t ldx, const float* weight, const float* bias, void* y,
+                               int32_t ldy, int32_t B, int32_t L, int32_t d, int32_t k, void* stream);
+/* dx, dweight [d][4], dbias [d] of the above (reference modules/fusion_blocks.py:264-292); the pre-activation is
+   recomputed from x.  ws: hs_causal_conv1d_ws_bytes(B, d) (per-batch partials, summed over b in order). */
+hs_status hs_causal_conv1d_bwd(int32_t dtype, const void* dy, int32_t lddy, const void* x, int32_t ldx, const float* weight,
+                               const float* bias, void* dx, int32_t lddx, float* dweight, float* dbias, void* ws,
+                               int64_t ws_bytes, int32_t B, int32_t L, int32_t d, int32_t k, void* stream);
+int64_t hs_causal_conv1d_ws_bytes(int32_t B, int32_t d);
+/* Selective scan (reference modules/fusion_blocks.py:264-292: Mamba's selective_scan_fn with delta_softplus, D and z):
+     delta = softplus(dt + dt_bias), A = -exp(A_log) [d][16]
+     h_t = exp(delta_t A) h_{t-1} + delta_t Bm_t u_t,  y_t = <h_t, Cm_t> + D u_t,  out_t = y_t silu(z_t)
+   Bm / Cm: [B*L][16] with the shared pitch ldbc.  hck (NULL in inference): f32 [B][(L-1)/chunk][d][16], the state after every
+   full chunk of hs_selective_scan_chunk_len() steps that has a successor, kept for the backward. */
+hs_status hs_selective_scan_fwd(int32_t dtype, const void* u, int32_t ldu, const void* dt, int32_t lddt, const float* dt_bias,
+                                const float* A_log, const void* Bm, const void* Cm, int32_t ldbc, const float* D, const void* z,
+                                int32_t ldz, void* out, int32_t ldo, float* hck, int32_t B, int32_t L, int32_t d, int32_t N,
+                                void* stream);
+/* Gradients of hs_selective_scan_fwd (reference modules/fusion_blocks.py:264-292): du, ddt (raw dt), dz [B*L][d], dBm / dCm
+   [B*L][16] (pitch lddbc, summed over channels), dA_log [d][16], dD [d], ddt_bias [d] (summed over batch and time).  The
+   states inside a chunk are recomputed from hck.  ws: hs_selective_scan_ws_bytes(B, L, d). */
+hs_status hs_selective_scan_bwd(int32_t dtype, const void* dout, int32_t lddo, const void* u, int32_t ldu, const void* dt,
+                                int32_t lddt, const float* dt_bias, const float* A_log, const void* Bm, const void* Cm,
+                                int32_t ldbc, const float* D, const void* z, int32_t ldz, const float* hck, void* du, int32_t lddu,
+                                void* ddt, int32_t ldddt, void* dBm, void* dCm, int32_t lddbc, void* dz, int32_t lddz,
+                                float* dA_log, float* dD, float* ddt_bias, void* ws, int64_t ws_bytes, int32_t B, int32_t L,
+                                int32_t d, int32_t N, void* stream);
+int64_t hs_selective_scan_ws_bytes(int32_t B, int32_t L, int32_t d);
+int32_t hs_selective_scan_chunk_len(void);
+/* out[b][t][:] = x[b][t][:] + v[b][:] (v f32): the pooled text feature added to every image token
+   (reference modules/fusion_blocks.py:264-292, `image_tokens + txt_feat`). */
+hs_status hs_add_token_bias_fwd(int32_t dtype, const void* x, const float* v, void* out, int32_t B, int32_t L, int32_t H,
+                                void* stream);
+/* dv[b][:] = sum_t dy[b][t][:] in time order (reference modules/fusion_blocks.py:264-292); dx is dy itself. */
+hs_status hs_add_token_bias_bwd(int32_t dtype, const void* dy, float* dv, int32_t B, int32_t L, int32_t H, void* stream);
+
 /* KANLinear.regularization_loss (reference ConNexT/models/block/kan1.py:216-236) on spline_weight viewed as
    [rows = out*in][coeffs]: loss = ra * sum_j l_j + re * entropy(l / sum l), l_j = mean_c |w[j][c]|; dw (optional) is
    d loss / d w.  Single workgroup, deterministic. */

@@ -256,6 +256,20 @@ def _declare(l):
     l.hs_lstm_cell_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
     l.hs_gru_cell_fwd.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, i32, vp]
     l.hs_gru_cell_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
+    l.hs_causal_conv1d_fwd.argtypes = [i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    l.hs_causal_conv1d_bwd.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, vp]
+    l.hs_causal_conv1d_ws_bytes.argtypes = [i32, i32]
+    l.hs_causal_conv1d_ws_bytes.restype = i64
+    l.hs_selective_scan_fwd.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32,
+                                        vp]
+    l.hs_selective_scan_bwd.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32,
+                                        vp, vp, i32, vp, i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]
+    l.hs_selective_scan_ws_bytes.argtypes = [i32, i32, i32]
+    l.hs_selective_scan_ws_bytes.restype = i64
+    l.hs_selective_scan_chunk_len.argtypes = []
+    l.hs_selective_scan_chunk_len.restype = i32
+    l.hs_add_token_bias_fwd.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp]
+    l.hs_add_token_bias_bwd.argtypes = [i32, vp, vp, i32, i32, i32, vp]
     l.hs_concat2_t.argtypes = [i32, vp, i32, vp, i32, vp, i64, vp]
     l.hs_split2_t.argtypes = [i32, vp, vp, i32, vp, i32, i64, vp]
     l.hs_prof_calibrate.argtypes = [vp, i32, C.POINTER(C.c_float)]

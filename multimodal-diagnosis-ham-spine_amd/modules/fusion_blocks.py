@@ -9,7 +9,8 @@ import torch.nn as nn
 
 from hamspine import functional as F
 from hamspine import small as S
-from hamspine.nn import LayerNorm, Linear, MultiheadAttention
+from hamspine import ssm
+from hamspine.nn import LayerNorm, Linear, Mamba, MultiheadAttention
 
 _LEVELS = ("layer2", "layer3", "layer4")
 
@@ -177,12 +178,25 @@ class BilinearFusionModule(_PooledFusion):
 
 
 class SSMFusionModule(nn.Module):
-    """The reference needs the external CUDA package `mamba_ssm` here (fusion_blocks.py:264-272); it is
-    not part of the reference tree, so this variant is out of scope and fails the same way."""
+    """mean_t(Mamba(img + Linear(pool(txt)))) (fusion_blocks.py:264-292).  The reference imports `mamba_ssm.Mamba`; here
+    the block is hamspine.nn.Mamba (same parameters and state-dict keys, HIP conv1d / selective-scan kernels).  The token
+    mean is taken before Mamba's bias-free out_proj."""
 
     def __init__(self, text_dim, hidden_dim, text_pool="cls"):
         super().__init__()
-        raise ImportError("SSM/Mamba fusion requires `mamba-ssm`, which has no MI355X build in this framework.")
+        self.text_pool = text_pool
+        self.txt_proj = Linear(text_dim, hidden_dim)
+        self.mamba = Mamba(d_model=hidden_dim)
+        self.pool = nn.AdaptiveAvgPool1d(1)
+
+    def _pool_text(self, text_tokens):
+        return pool_text_tokens(text_tokens, self.text_pool)
+
+    def forward(self, image_tokens, text_tokens, txt_mask=None):
+        if isinstance(image_tokens, dict):
+            raise ValueError("SSMFusionModule expects single-scale image tokens.")
+        txt_feat = self.txt_proj(self._pool_text(text_tokens))              # (B, H) f32
+        return self.mamba(ssm.add_token_bias(image_tokens, txt_feat), mean_tokens=True)
 
 
 class VMambaFusionModule(nn.Module):
