@@ -466,12 +466,31 @@ hs_status hs_selective_scan_bwd(int32_t dtype, const void* dout, int32_t lddo, c
                                 int32_t d, int32_t N, void* stream);
 int64_t hs_selective_scan_ws_bytes(int32_t B, int32_t L, int32_t d);
 int32_t hs_selective_scan_chunk_len(void);
+/* The scan above for N = d_state in {16, 32, 64, 128, 256} (reference ConNexT/models/block/len4mamba.py:74-79,138-143:
+   Mamba(d_state=128)): every [16] above reads [N], hck is [B][(L-1)/chunk][d][N], and for N > 16 A_log, Bm, Cm and hck must
+   be 16-byte aligned.  Steps between saved states for this N (16 at N <= 64, 8 at 128, 4 at 256); -1 for any other N. */
+int32_t hs_selective_scan_chunk_len_n(int32_t N);
+/* Workspace of hs_selective_scan_bwd at d_state N (reference ConNexT/models/block/len4mamba.py:74-79,138-143): per-block
+   partials [ceil(d/16)][B*L][2N] and per-batch partials [B][d][N + 2], f32; -1 for an unsupported N. */
+int64_t hs_selective_scan_ws_bytes_n(int32_t B, int32_t L, int32_t d, int32_t N);
 /* out[b][t][:] = x[b][t][:] + v[b][:] (v f32): the pooled text feature added to every image token
    (reference modules/fusion_blocks.py:264-292, `image_tokens + txt_feat`). */
 hs_status hs_add_token_bias_fwd(int32_t dtype, const void* x, const float* v, void* out, int32_t B, int32_t L, int32_t H,
                                 void* stream);
 /* dv[b][:] = sum_t dy[b][t][:] in time order (reference modules/fusion_blocks.py:264-292); dx is dy itself. */
 hs_status hs_add_token_bias_bwd(int32_t dtype, const void* dy, float* dv, int32_t B, int32_t L, int32_t H, void* stream);
+/* Token sequence of the multimodal Mamba blocks (reference ConNexT/models/block/len4mamba.py:86-106,147-168), f32:
+   seq[b] = [text[b]; img[b][0..P-1]; first[b]; last[b]] + pe[0..P+2], rows of H = proj_dim; replaces torch.cat and the
+   broadcast add of the positional encoding. */
+hs_status hs_token_seq_assemble_fwd(const float* text, const float* img, const float* first, const float* last, const float* pe,
+                                    float* seq, int32_t B, int32_t P, int32_t H, void* stream);
+/* The rows of dseq [B][P+3][H] handed back to the four projections (reference ConNexT/models/block/len4mamba.py:86-106);
+   a NULL output is skipped. */
+hs_status hs_token_seq_assemble_bwd(const float* dseq, float* dtext, float* dimg, float* dfirst, float* dlast, int32_t B,
+                                    int32_t P, int32_t H, void* stream);
+/* dst[b][c][r] = src[b][r][c], f32: `img.permute(0, 2, 1)` of reference ConNexT/models/block/len4mamba.py:93,155 as the
+   (B P, C) rows the projection GEMM reads; the same call with R and C swapped is its backward. */
+hs_status hs_transpose_batched_f32(const float* src, float* dst, int32_t B, int32_t R, int32_t C, void* stream);
 
 /* KANLinear.regularization_loss (reference ConNexT/models/block/kan1.py:216-236) on spline_weight viewed as
    [rows = out*in][coeffs]: loss = ra * sum_j l_j + re * entropy(l / sum l), l_j = mean_c |w[j][c]|; dw (optional) is

@@ -268,8 +268,15 @@ def _declare(l):
     l.hs_selective_scan_ws_bytes.restype = i64
     l.hs_selective_scan_chunk_len.argtypes = []
     l.hs_selective_scan_chunk_len.restype = i32
+    l.hs_selective_scan_chunk_len_n.argtypes = [i32]
+    l.hs_selective_scan_chunk_len_n.restype = i32
+    l.hs_selective_scan_ws_bytes_n.argtypes = [i32, i32, i32, i32]
+    l.hs_selective_scan_ws_bytes_n.restype = i64
     l.hs_add_token_bias_fwd.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp]
     l.hs_add_token_bias_bwd.argtypes = [i32, vp, vp, i32, i32, i32, vp]
+    l.hs_token_seq_assemble_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    l.hs_token_seq_assemble_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    l.hs_transpose_batched_f32.argtypes = [vp, vp, i32, i32, i32, vp]
     l.hs_concat2_t.argtypes = [i32, vp, i32, vp, i32, vp, i64, vp]
     l.hs_split2_t.argtypes = [i32, vp, vp, i32, vp, i32, i64, vp]
     l.hs_prof_calibrate.argtypes = [vp, i32, C.POINTER(C.c_float)]

@@ -1,11 +1,13 @@
-// Mamba block of the SSM fusion (reference modules/fusion_blocks.py:264-292 -> mamba_ssm.Mamba, d_state 16, d_conv 4):
-// causal depthwise conv1d + SiLU, the selective scan, and the broadcast add of the text feature; forward and backward.
+// Mamba block of the SSM fusion (reference modules/fusion_blocks.py:264-292 -> mamba_ssm.Mamba, d_state 16, d_conv 4) and of the
+// multimodal Mamba blocks (reference ConNexT/models/block/len4mamba.py:74-79,138-143, d_state 128): causal depthwise conv1d +
+// SiLU, the selective scan, the broadcast add of the text feature and the token sequence of len4mamba; forward and backward.
 //
-// Scan mapping: 16 lanes per (batch, channel) pair, lane = state index n.  One 64-lane wave carries 4 channels, a 256-thread
-// block 16 consecutive channels of one batch element.  The per-step sum over the 16 states is four DPP adds inside one
-// 16-lane row (no LDS, no ds_bpermute), Bm_t / Cm_t are one 16-wide load that the four rows of a wave share, and B*d/4 waves
-// (8192 at B 64, d 512: 32 per CU) hide the latency of the dependent chain over L.  The price is that the per-channel
-// scalars (softplus, SiLU) are computed by all 16 lanes of a row.
+// Scan mapping, described for d_state 16 (S = 1; for more states see chunk_for below): 16 lanes per (batch, channel) pair,
+// lane = state index n.  One 64-lane wave carries 4 channels, a 256-thread block 16 consecutive channels of one batch
+// element.  The per-step sum over the 16 states is four DPP adds inside one 16-lane row (no LDS, no ds_bpermute), Bm_t / Cm_t
+// are one 16-wide load that the four rows of a wave share, and B*d/4 waves (8192 at B 64, d 512: 32 per CU) hide the latency
+// of the dependent chain over L.  The price is that the per-channel scalars (softplus, SiLU) are computed by all 16 lanes of
+// a row.
 //
 // Backward: the forward keeps h only after every full chunk of kChunk steps; the backward walks the chunks last to first,
 // recomputes the kChunk states of a chunk into registers and then runs the reverse recurrence over them.
@@ -17,8 +19,15 @@
 
 namespace hs {
 
-static constexpr int kChunk = 16;    // steps between saved states (= registers the backward spends on recomputed states)
-static constexpr int kStates = 16;
+// Lane n of the 16 lanes of a (batch, channel) pair holds the S = N / 16 consecutive states n*S .. n*S + S - 1 in registers
+// (N = d_state in {16, 32, 64, 128, 256}; ConNexT/models/block/len4mamba.py:74-79,138-143 builds d_state 128).  S = 1 is the
+// kernel of the SSM fusion.  chunk_for(S): steps between saved states; the backward keeps chunk x S recomputed states in
+// registers, so the chunk shrinks as S grows (at most 64 of them).  steps_for(S): steps whose operands the forward requests
+// together (2 S values per step and lane).
+static constexpr int kLanes = 16;
+__host__ __device__ constexpr int chunk_for(int S) { return S <= 4 ? 16 : (S == 8 ? 8 : 4); }
+__host__ __device__ constexpr int steps_for(int S) { return S <= 8 ? 4 : 2; }
+static constexpr int kChunk = chunk_for(1);
 
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
 // torch.nn.functional.softplus (threshold 20); log1pf keeps the relative precision of small dt
@@ -105,58 +114,98 @@ __global__ void causal_conv1d_bwd_reduce_kernel(const float* __restrict__ part, 
 // ------------------------------------------------------------------------------------------------------------
 // selective scan
 // ------------------------------------------------------------------------------------------------------------
-template <typename T>
+// the S states of one lane as 16-byte (or smaller) loads; the S = 1 case is one scalar load
+template <typename T, int S> struct alignas(S * sizeof(T) < 16 ? S * sizeof(T) : 16) StatePack {
+    T e[(S * sizeof(T) < 16 ? S * sizeof(T) : 16) / sizeof(T)];
+};
+template <typename T, int S>
+__device__ __forceinline__ void load_states(const T* __restrict__ p, float (&v)[S]) {
+    using P = StatePack<T, S>;
+    constexpr int kPer = sizeof(P) / sizeof(T);
+#pragma unroll
+    for (int i = 0; i < S / kPer; ++i) {
+        const P q = reinterpret_cast<const P*>(p)[i];
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) v[i * kPer + j] = to_f32(q.e[j]);
+    }
+}
+template <int S>
+__device__ __forceinline__ void store_states(float* __restrict__ p, const float (&v)[S]) {
+    using P = StatePack<float, S>;
+    constexpr int kPer = sizeof(P) / sizeof(float);
+#pragma unroll
+    for (int i = 0; i < S / kPer; ++i) {
+        P q;
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) q.e[j] = v[i * kPer + j];
+        reinterpret_cast<P*>(p)[i] = q;
+    }
+}
+
+template <typename T, int S>
 __global__ __launch_bounds__(256) void selective_scan_fwd_kernel(const T* __restrict__ u, int ldu, const T* __restrict__ dt,
                                                                  int lddt, const float* __restrict__ dt_bias,
                                                                  const float* __restrict__ A_log, const T* __restrict__ Bm,
                                                                  const T* __restrict__ Cm, int ldbc, const float* __restrict__ D,
                                                                  const T* __restrict__ z, int ldz, T* __restrict__ out, int ldo,
                                                                  float* __restrict__ hck, int L, int d) {
+    constexpr int N = kLanes * S, kCh = chunk_for(S), kSt = steps_for(S);
     const int n = threadIdx.x & 15;
     const int ch = blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool valid = ch < d;
     const int cc = valid ? ch : d - 1;          // lanes past the last channel compute on a copy and store nothing
     const int b = blockIdx.y;
     const long long r0 = (long long)b * L;
-    const float A = -__expf(A_log[cc * kStates + n]);
-    const float Dv = D[cc], bias = dt_bias[cc];
-    const int nck = (L - 1) / kChunk;
-    float h = 0.f;
-    for (int t0 = 0; t0 < L; t0 += 4) {
-        float uu[4], rr[4], bb[4], cv[4], zz[4];
+    float A[S], h[S];
+    load_states<float, S>(A_log + (cc * N + n * S), A);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {           // the four steps' operands are requested together
+    for (int s = 0; s < S; ++s) {
+        A[s] = -__expf(A[s]);
+        h[s] = 0.f;
+    }
+    const float Dv = D[cc], bias = dt_bias[cc];
+    const int nck = (L - 1) / kCh;
+    for (int t0 = 0; t0 < L; t0 += kSt) {
+        float uu[kSt], rr[kSt], bb[kSt][S], cv[kSt][S], zz[kSt];
+#pragma unroll
+        for (int j = 0; j < kSt; ++j) {         // the steps' operands are requested together
             const long long r = r0 + min(t0 + j, L - 1);
             uu[j] = to_f32(u[r * ldu + cc]);
             rr[j] = to_f32(dt[r * lddt + cc]);
-            bb[j] = to_f32(Bm[r * ldbc + n]);
-            cv[j] = to_f32(Cm[r * ldbc + n]);
+            load_states<T, S>(Bm + (r * ldbc + n * S), bb[j]);
+            load_states<T, S>(Cm + (r * ldbc + n * S), cv[j]);
             zz[j] = to_f32(z[r * ldz + cc]);
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < kSt; ++j) {
             const int t = t0 + j;
             if (t < L) {
                 const float dl = softplus_f(rr[j] + bias);
-                h = fmaf(__expf(dl * A), h, dl * bb[j] * uu[j]);
-                const float y = row_sum16(h * cv[j]) + Dv * uu[j];
+                float p;                        // the lane's S products first, the row sum finishes
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    h[s] = fmaf(__expf(dl * A[s]), h[s], dl * bb[j][s] * uu[j]);
+                    p = s == 0 ? h[0] * cv[j][0] : fmaf(h[s], cv[j][s], p);
+                }
+                const float y = row_sum16(p) + Dv * uu[j];
                 if (n == 0 && valid) out[(r0 + t) * ldo + ch] = from_f32<T>(y * zz[j] * sigmoid_f(zz[j]));
-                if (hck && ((t + 1) % kChunk) == 0 && t + 1 < L && valid)
-                    hck[((((long long)b * nck) + (t + 1) / kChunk - 1) * d + ch) * kStates + n] = h;
+                if (hck && ((t + 1) % kCh) == 0 && t + 1 < L && valid)
+                    store_states<S>(hck + (((((long long)b * nck) + (t + 1) / kCh - 1) * d + ch) * N + n * S), h);
             }
         }
     }
 }
 
-// part_bc: [nblk][B*L][32] (dBm | dCm summed over the 16 channels of a block); part_p: [B][d][18] (dA_log[16], dD, ddt_bias)
-template <typename T>
+// part_bc: [nblk][B*L][2N] (dBm | dCm summed over the 16 channels of a block); part_p: [B][d][N + 2] (dA_log[N], dD, ddt_bias)
+template <typename T, int S>
 __global__ __launch_bounds__(256) void selective_scan_bwd_kernel(
     const T* __restrict__ dout, int lddo, const T* __restrict__ u, int ldu, const T* __restrict__ dt, int lddt,
     const float* __restrict__ dt_bias, const float* __restrict__ A_log, const T* __restrict__ Bm, const T* __restrict__ Cm,
     int ldbc, const float* __restrict__ D, const T* __restrict__ z, int ldz, const float* __restrict__ hck, T* __restrict__ du,
     int lddu, T* __restrict__ ddt, int ldddt, T* __restrict__ dz, int lddz, float* __restrict__ part_bc,
     float* __restrict__ part_p, int B, int L, int d) {
-    __shared__ float sbc[4][kChunk][32];
+    constexpr int N = kLanes * S, kCh = chunk_for(S);
+    __shared__ float sbc[4][kCh][2 * N];
     const int tid = threadIdx.x;
     const int n = tid & 15, wave = tid >> 6, lane = tid & 63;
     const int ch = blockIdx.x * 16 + (tid >> 4);
@@ -165,50 +214,77 @@ __global__ __launch_bounds__(256) void selective_scan_bwd_kernel(
     const int b = blockIdx.y;
     const long long r0 = (long long)b * L;
     const long long rows = (long long)B * L;
-    const float A = -__expf(A_log[cc * kStates + n]);
-    const float Dv = D[cc], bias = dt_bias[cc];
-    const int nchunks = (L + kChunk - 1) / kChunk;
-    const int nck = nchunks - 1;
-    float dh = 0.f, accA = 0.f, accD = 0.f, accB = 0.f;
-    for (int c = nchunks - 1; c >= 0; --c) {
-        const int t0 = c * kChunk;
-        const int len = min(kChunk, L - t0);    // the same for the whole block
-        float hs[kChunk];                        // hs[i]: the state before step t0 + i
-        {
-            float h = c > 0 ? hck[(((long long)b * nck + (c - 1)) * d + cc) * kStates + n] : 0.f;
+    float A[S], dh[S], accA[S];
+    load_states<float, S>(A_log + (cc * N + n * S), A);
 #pragma unroll
-            for (int i = 0; i < kChunk; ++i) {
-                hs[i] = h;
+    for (int s = 0; s < S; ++s) {
+        A[s] = -__expf(A[s]);
+        dh[s] = 0.f;
+        accA[s] = 0.f;
+    }
+    const float Dv = D[cc], bias = dt_bias[cc];
+    const int nchunks = (L + kCh - 1) / kCh;
+    const int nck = nchunks - 1;
+    float accD = 0.f, accB = 0.f;
+    for (int c = nchunks - 1; c >= 0; --c) {
+        const int t0 = c * kCh;
+        const int len = min(kCh, L - t0);       // the same for the whole block
+        float hs[kCh][S];                        // hs[i]: the state before step t0 + i
+        {
+            float h[S];
+#pragma unroll
+            for (int s = 0; s < S; ++s) h[s] = 0.f;
+            if (c > 0) load_states<float, S>(hck + ((((long long)b * nck + (c - 1)) * d + cc) * N + n * S), h);
+#pragma unroll
+            for (int i = 0; i < kCh; ++i) {
+#pragma unroll
+                for (int s = 0; s < S; ++s) hs[i][s] = h[s];
                 if (i < len - 1) {               // the state after the chunk's last step is not needed here
                     const long long r = r0 + t0 + i;
                     const float dl = softplus_f(to_f32(dt[r * lddt + cc]) + bias);
-                    h = fmaf(__expf(dl * A), h, dl * to_f32(Bm[r * ldbc + n]) * to_f32(u[r * ldu + cc]));
+                    float bn[S];
+                    load_states<T, S>(Bm + (r * ldbc + n * S), bn);
+                    const float uv = to_f32(u[r * ldu + cc]);
+#pragma unroll
+                    for (int s = 0; s < S; ++s) h[s] = fmaf(__expf(dl * A[s]), h[s], dl * bn[s] * uv);
                 }
             }
         }
 #pragma unroll
-        for (int i = kChunk - 1; i >= 0; --i) {
+        for (int i = kCh - 1; i >= 0; --i) {
             if (i < len) {
                 const long long r = r0 + t0 + i;
                 const float uv = to_f32(u[r * ldu + cc]);
                 const float pre = to_f32(dt[r * lddt + cc]) + bias;
-                const float bn = to_f32(Bm[r * ldbc + n]);
-                const float cn = to_f32(Cm[r * ldbc + n]);
+                float bn[S], cn[S];
+                load_states<T, S>(Bm + (r * ldbc + n * S), bn);
+                load_states<T, S>(Cm + (r * ldbc + n * S), cn);
                 const float zv = to_f32(z[r * ldz + cc]);
                 const float g = to_f32(dout[r * lddo + cc]);
                 const float dl = softplus_f(pre);
-                const float a = __expf(dl * A);
-                const float hp = hs[i];
-                const float ht = fmaf(a, hp, dl * bn * uv);
-                const float y = row_sum16(ht * cn) + Dv * uv;
+                float a[S], ht[S], p;
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    a[s] = __expf(dl * A[s]);
+                    ht[s] = fmaf(a[s], hs[i][s], dl * bn[s] * uv);
+                    p = s == 0 ? ht[0] * cn[0] : fmaf(ht[s], cn[s], p);
+                }
+                const float y = row_sum16(p) + Dv * uv;
                 const float sz = sigmoid_f(zv);
                 const float dy = g * zv * sz;
                 const float dzv = g * y * sz * (1.f + zv * (1.f - sz));
-                dh = fmaf(dy, cn, dh);                        // d loss / d h_t
-                const float s1 = row_sum16(dh * bn);
-                const float s2 = row_sum16(dh * hp * a * A);
+                float p1, p2;
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    dh[s] = fmaf(dy, cn[s], dh[s]);               // d loss / d h_t
+                    p1 = s == 0 ? dh[0] * bn[0] : fmaf(dh[s], bn[s], p1);
+                    p2 = s == 0 ? dh[0] * hs[i][0] * a[0] * A[0] : fmaf(dh[s] * hs[i][s] * a[s], A[s], p2);
+                }
+                const float s1 = row_sum16(p1);
+                const float s2 = row_sum16(p2);
                 const float dr = (uv * s1 + s2) * sigmoid_f(pre);     // through delta = softplus(dt + bias)
-                accA = fmaf(dh * hp, a * dl, accA);
+#pragma unroll
+                for (int s = 0; s < S; ++s) accA[s] = fmaf(dh[s] * hs[i][s], a[s] * dl, accA[s]);
                 accD = fmaf(dy, uv, accD);
                 accB += dr;
                 if (n == 0 && valid) {
@@ -217,57 +293,63 @@ __global__ __launch_bounds__(256) void selective_scan_bwd_kernel(
                     dz[r * lddz + ch] = from_f32<T>(dzv);
                 }
                 // dBm_t[n], dCm_t[n]: sum over the wave's 4 channels here, over the block's 4 waves below
-                float vb = valid ? dh * dl * uv : 0.f;
-                float vc = valid ? dy * ht : 0.f;
-                vb += __shfl_xor(vb, 16, 64);
-                vc += __shfl_xor(vc, 16, 64);
-                vb += __shfl_xor(vb, 32, 64);
-                vc += __shfl_xor(vc, 32, 64);
-                if (lane < 16) {
-                    sbc[wave][i][n] = vb;
-                    sbc[wave][i][16 + n] = vc;
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    float vb = valid ? dh[s] * dl * uv : 0.f;
+                    float vc = valid ? dy * ht[s] : 0.f;
+                    vb += __shfl_xor(vb, 16, 64);
+                    vc += __shfl_xor(vc, 16, 64);
+                    vb += __shfl_xor(vb, 32, 64);
+                    vc += __shfl_xor(vc, 32, 64);
+                    if (lane < 16) {
+                        sbc[wave][i][n * S + s] = vb;
+                        sbc[wave][i][N + n * S + s] = vc;
+                    }
+                    dh[s] *= a[s];                                // carried to step t - 1
                 }
-                dh *= a;                                      // carried to step t - 1
             }
         }
         __syncthreads();
-        for (int e = tid; e < len * 32; e += 256) {
-            const int i = e >> 5, j = e & 31;
+        for (int e = tid; e < len * 2 * N; e += 256) {
+            const int i = e / (2 * N), j = e % (2 * N);
             const float s = (sbc[0][i][j] + sbc[1][i][j]) + (sbc[2][i][j] + sbc[3][i][j]);
-            part_bc[((long long)blockIdx.x * rows + r0 + t0 + i) * 32 + j] = s;
+            part_bc[((long long)blockIdx.x * rows + r0 + t0 + i) * (2 * N) + j] = s;
         }
         __syncthreads();
     }
     if (valid) {
-        float* p = part_p + ((long long)b * d + ch) * 18;
-        p[n] = accA * A;                                       // dA/dA_log = A
+        float* p = part_p + ((long long)b * d + ch) * (N + 2);
+#pragma unroll
+        for (int s = 0; s < S; ++s) p[n * S + s] = accA[s] * A[s];    // dA/dA_log = A
         if (n == 0) {
-            p[16] = accD;
-            p[17] = accB;
+            p[N] = accD;
+            p[N + 1] = accB;
         }
     }
 }
+// sh = log2(2N): N is a power of two
 template <typename T>
 __global__ void selective_scan_bwd_reduce_kernel(const float* __restrict__ part_bc, const float* __restrict__ part_p, int nblk,
-                                                 long long rows, int B, int d, T* __restrict__ dBm, T* __restrict__ dCm,
-                                                 int lddbc, float* __restrict__ dA_log, float* __restrict__ dD,
-                                                 float* __restrict__ ddt_bias) {
-    const long long nbc = rows * 32, np = (long long)d * 18;
+                                                 long long rows, int B, int d, int N, int sh, T* __restrict__ dBm,
+                                                 T* __restrict__ dCm, int lddbc, float* __restrict__ dA_log,
+                                                 float* __restrict__ dD, float* __restrict__ ddt_bias) {
+    const int np1 = N + 2;
+    const long long nbc = rows << sh, np = (long long)d * np1;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nbc + np; i += (long long)gridDim.x * 256) {
         if (i < nbc) {
             float acc = 0.f;
             for (int k = 0; k < nblk; ++k) acc += part_bc[(long long)k * nbc + i];
-            const long long r = i >> 5;
-            const int j = (int)(i & 31);
-            if (j < 16) dBm[r * lddbc + j] = from_f32<T>(acc);
-            else dCm[r * lddbc + j - 16] = from_f32<T>(acc);
+            const long long r = i >> sh;
+            const int j = (int)(i & (2 * N - 1));
+            if (j < N) dBm[r * lddbc + j] = from_f32<T>(acc);
+            else dCm[r * lddbc + j - N] = from_f32<T>(acc);
         } else {
             const long long e = i - nbc;
-            const int c = (int)(e / 18), j = (int)(e - (long long)c * 18);
+            const int c = (int)(e / np1), j = (int)(e - (long long)c * np1);
             float acc = 0.f;
-            for (int b = 0; b < B; ++b) acc += part_p[((long long)b * d + c) * 18 + j];
-            if (j < 16) dA_log[c * 16 + j] = acc;
-            else if (j == 16) dD[c] = acc;
+            for (int b = 0; b < B; ++b) acc += part_p[((long long)b * d + c) * np1 + j];
+            if (j < N) dA_log[c * N + j] = acc;
+            else if (j == N) dD[c] = acc;
             else ddt_bias[c] = acc;
         }
     }
@@ -294,6 +376,62 @@ __global__ void add_token_bias_bwd_kernel(const T* __restrict__ dy, float* __res
     dv[i] = acc;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// token sequence of the multimodal Mamba blocks (reference ConNexT/models/block/len4mamba.py:86-106,147-168), f32
+// ------------------------------------------------------------------------------------------------------------
+// dst[b][c][r] = src[b][r][c]: the (B, C, P) image feature as the (B P, C) rows the projection GEMM reads; its own backward
+__global__ __launch_bounds__(256) void transpose_batched_kernel(const float* __restrict__ src, float* __restrict__ dst, int R,
+                                                                int C) {
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+    const long long base = (long long)blockIdx.z * R * C;
+    for (int k = ty; k < 32; k += 8) {
+        const int r = r0 + k, c = c0 + tx;
+        if (r < R && c < C) tile[k][tx] = src[base + (long long)r * C + c];
+    }
+    __syncthreads();
+    for (int k = ty; k < 32; k += 8) {
+        const int c = c0 + k, r = r0 + tx;
+        if (r < R && c < C) dst[base + (long long)c * R + r] = tile[tx][k];
+    }
+}
+// seq[b] = [text[b]; img[b][0..P-1]; first[b]; last[b]] + pe[0..P+2], every row H wide
+__global__ void token_seq_assemble_kernel(const float* __restrict__ text, const float* __restrict__ img,
+                                          const float* __restrict__ first, const float* __restrict__ last,
+                                          const float* __restrict__ pe, float* __restrict__ seq, int B, int P, int H) {
+    const int Lt = P + 3;
+    const long long n = (long long)B * Lt * H;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int h = (int)(i % H);
+        const long long row = i / H;
+        const int t = (int)(row % Lt);
+        const long long b = row / Lt;
+        float v;
+        if (t == 0) v = text[b * H + h];
+        else if (t <= P) v = img[(b * P + t - 1) * H + h];
+        else if (t == P + 1) v = first[b * H + h];
+        else v = last[b * H + h];
+        seq[i] = v + pe[(long long)t * H + h];
+    }
+}
+__global__ void token_seq_assemble_bwd_kernel(const float* __restrict__ dseq, float* __restrict__ dtext, float* __restrict__ dimg,
+                                              float* __restrict__ dfirst, float* __restrict__ dlast, int B, int P, int H) {
+    const int Lt = P + 3;
+    const long long n = (long long)B * Lt * H;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int h = (int)(i % H);
+        const long long row = i / H;
+        const int t = (int)(row % Lt);
+        const long long b = row / Lt;
+        const float g = dseq[i];
+        if (t == 0) { if (dtext) dtext[b * H + h] = g; }
+        else if (t <= P) { if (dimg) dimg[(b * P + t - 1) * H + h] = g; }
+        else if (t == P + 1) { if (dfirst) dfirst[b * H + h] = g; }
+        else if (dlast) dlast[b * H + h] = g;
+    }
+}
+
 static inline int grid_for(long long n, int cap = 4096) {
     return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, cap));
 }
@@ -306,6 +444,33 @@ static inline bool pitch_ok(int ld, int width, int esz) { return ld >= width && 
             return HS_ERR_UNSUPPORTED;                                                       \
         }                                                                                    \
     } while (0)
+
+template <typename T, int S>
+static void launch_scan_fwd(const void* u, int ldu, const void* dt, int lddt, const float* dt_bias, const float* A_log,
+                            const void* Bm, const void* Cm, int ldbc, const float* D, const void* z, int ldz, void* out, int ldo,
+                            float* hck, int B, int L, int d, hipStream_t stream) {
+    hipLaunchKernelGGL((selective_scan_fwd_kernel<T, S>), dim3(ceil_div(d, 16), B), dim3(256), 0, stream, (const T*)u, ldu,
+                       (const T*)dt, lddt, dt_bias, A_log, (const T*)Bm, (const T*)Cm, ldbc, D, (const T*)z, ldz, (T*)out, ldo,
+                       hck, L, d);
+}
+template <typename T, int S>
+static void launch_scan_bwd(const void* dout, int lddo, const void* u, int ldu, const void* dt, int lddt, const float* dt_bias,
+                            const float* A_log, const void* Bm, const void* Cm, int ldbc, const float* D, const void* z, int ldz,
+                            const float* hck, void* du, int lddu, void* ddt, int ldddt, void* dz, int lddz, float* part_bc,
+                            float* part_p, int B, int L, int d, hipStream_t stream) {
+    hipLaunchKernelGGL((selective_scan_bwd_kernel<T, S>), dim3(ceil_div(d, 16), B), dim3(256), 0, stream, (const T*)dout, lddo,
+                       (const T*)u, ldu, (const T*)dt, lddt, dt_bias, A_log, (const T*)Bm, (const T*)Cm, ldbc, D, (const T*)z,
+                       ldz, hck, (T*)du, lddu, (T*)ddt, ldddt, (T*)dz, lddz, part_bc, part_p, B, L, d);
+}
+// one case per supported d_state; S = N / 16
+#define HS_SCAN_DISPATCH(fn, T, ...)                       \
+    switch (N) {                                           \
+        case 16: fn<T, 1>(__VA_ARGS__); break;             \
+        case 32: fn<T, 2>(__VA_ARGS__); break;             \
+        case 64: fn<T, 4>(__VA_ARGS__); break;             \
+        case 128: fn<T, 8>(__VA_ARGS__); break;            \
+        default: fn<T, 16>(__VA_ARGS__); break;            \
+    }
 
 }  // namespace hs
 
@@ -359,14 +524,22 @@ hs_status hs_causal_conv1d_bwd(int32_t dtype, const void* dy, int32_t lddy, cons
     return HS_OK;
 }
 
+// states per lane for a supported d_state, 0 otherwise
+static inline int states_per_lane(int N) { return (N == 16 || N == 32 || N == 64 || N == 128 || N == 256) ? N / kLanes : 0; }
 int32_t hs_selective_scan_chunk_len(void) { return kChunk; }
+int32_t hs_selective_scan_chunk_len_n(int32_t N) {
+    const int S = states_per_lane(N);
+    return S ? chunk_for(S) : -1;
+}
 static int scan_args_ok(const char* who, int32_t dtype, int32_t B, int32_t L, int32_t d, int32_t N) {
     HS_REQUIRE(dtype == HS_F32 || dtype == HS_BF16, "%s: bad dtype %d", who, dtype);
-    HS_SUPPORTED(N == kStates, "%s: d_state %d is not supported (only 16)", who, N);
+    HS_SUPPORTED(states_per_lane(N) != 0, "%s: d_state %d is not supported (only 16, 32, 64, 128, 256)", who, N);
     HS_SUPPORTED(B > 0 && L > 0 && d > 0, "%s: empty shape B %d L %d d %d", who, B, L, d);
     HS_SUPPORTED(B <= 65535, "%s: batch %d exceeds the grid limit 65535", who, B);
     return HS_OK;
 }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 hs_status hs_selective_scan_fwd(int32_t dtype, const void* u, int32_t ldu, const void* dt, int32_t lddt, const float* dt_bias,
                                 const float* A_log, const void* Bm, const void* Cm, int32_t ldbc, const float* D, const void* z,
                                 int32_t ldz, void* out, int32_t ldo, float* hck, int32_t B, int32_t L, int32_t d, int32_t N,
@@ -375,25 +548,27 @@ hs_status hs_selective_scan_fwd(int32_t dtype, const void* u, int32_t ldu, const
     HS_REQUIRE(u && dt && dt_bias && A_log && Bm && Cm && D && z && out, "selective_scan_fwd: null argument");
     const int esz = dtype == HS_BF16 ? 2 : 4;
     HS_SUPPORTED(pitch_ok(ldu, d, esz) && pitch_ok(lddt, d, esz) && pitch_ok(ldz, d, esz) && pitch_ok(ldo, d, esz) &&
-                     pitch_ok(ldbc, kStates, esz),
-                 "selective_scan_fwd: row pitches (u %d, dt %d, z %d, out %d >= d = %d; Bm/Cm %d >= 16) must be multiples of 16 bytes",
-                 ldu, lddt, ldz, ldo, d, ldbc);
-    const dim3 grid(ceil_div(d, 16), B);
-    if (dtype == HS_BF16)
-        hipLaunchKernelGGL(selective_scan_fwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)u, ldu,
-                           (const bf16_t*)dt, lddt, dt_bias, A_log, (const bf16_t*)Bm, (const bf16_t*)Cm, ldbc, D,
-                           (const bf16_t*)z, ldz, (bf16_t*)out, ldo, hck, L, d);
-    else
-        hipLaunchKernelGGL(selective_scan_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)u, ldu,
-                           (const float*)dt, lddt, dt_bias, A_log, (const float*)Bm, (const float*)Cm, ldbc, D, (const float*)z,
-                           ldz, (float*)out, ldo, hck, L, d);
+                     pitch_ok(ldbc, N, esz),
+                 "selective_scan_fwd: row pitches (u %d, dt %d, z %d, out %d >= d = %d; Bm/Cm %d >= %d) must be multiples of 16 bytes",
+                 ldu, lddt, ldz, ldo, d, ldbc, N);
+    HS_SUPPORTED(N == 16 || (aligned16(A_log) && aligned16(Bm) && aligned16(Cm) && aligned16(hck)),
+                 "selective_scan_fwd: A_log, Bm, Cm and hck must be 16-byte aligned for d_state %d", N);
+    if (dtype == HS_BF16) {
+        HS_SCAN_DISPATCH(launch_scan_fwd, bf16_t, u, ldu, dt, lddt, dt_bias, A_log, Bm, Cm, ldbc, D, z, ldz, out, ldo, hck, B, L,
+                         d, (hipStream_t)stream);
+    } else {
+        HS_SCAN_DISPATCH(launch_scan_fwd, float, u, ldu, dt, lddt, dt_bias, A_log, Bm, Cm, ldbc, D, z, ldz, out, ldo, hck, B, L,
+                         d, (hipStream_t)stream);
+    }
     HS_LAUNCH_CHECK();
     return HS_OK;
 }
-int64_t hs_selective_scan_ws_bytes(int32_t B, int32_t L, int32_t d) {
+int64_t hs_selective_scan_ws_bytes_n(int32_t B, int32_t L, int32_t d, int32_t N) {
+    if (!states_per_lane(N)) return -1;
     const long long nblk = ceil_div(d, 16);
-    return (nblk * B * L * 32 + (long long)B * d * 18) * 4;
+    return (nblk * B * L * 2 * N + (long long)B * d * (N + 2)) * 4;
 }
+int64_t hs_selective_scan_ws_bytes(int32_t B, int32_t L, int32_t d) { return hs_selective_scan_ws_bytes_n(B, L, d, 16); }
 hs_status hs_selective_scan_bwd(int32_t dtype, const void* dout, int32_t lddo, const void* u, int32_t ldu, const void* dt,
                                 int32_t lddt, const float* dt_bias, const float* A_log, const void* Bm, const void* Cm,
                                 int32_t ldbc, const float* D, const void* z, int32_t ldz, const float* hck, void* du, int32_t lddu,
@@ -402,37 +577,36 @@ hs_status hs_selective_scan_bwd(int32_t dtype, const void* dout, int32_t lddo, c
                                 int32_t d, int32_t N, void* stream) {
     HS_PROPAGATE(scan_args_ok("selective_scan_bwd", dtype, B, L, d, N));
     HS_REQUIRE(dout && u && dt && dt_bias && A_log && Bm && Cm && D && z && du && ddt && dBm && dCm && dz && dA_log && dD &&
-                   ddt_bias && ws && (hck || L <= kChunk),
+                   ddt_bias && ws && (hck || L <= hs_selective_scan_chunk_len_n(N)),
                "selective_scan_bwd: null argument");
     const int esz = dtype == HS_BF16 ? 2 : 4;
     HS_SUPPORTED(pitch_ok(lddo, d, esz) && pitch_ok(ldu, d, esz) && pitch_ok(lddt, d, esz) && pitch_ok(ldz, d, esz) &&
-                     pitch_ok(lddu, d, esz) && pitch_ok(ldddt, d, esz) && pitch_ok(lddz, d, esz) && pitch_ok(ldbc, kStates, esz) &&
-                     pitch_ok(lddbc, kStates, esz),
-                 "selective_scan_bwd: row pitches must cover their rows (d = %d, Bm/Cm 16) and be multiples of 16 bytes", d);
-    HS_REQUIRE(ws_bytes >= hs_selective_scan_ws_bytes(B, L, d), "selective_scan_bwd: workspace of %lld bytes is too small",
+                     pitch_ok(lddu, d, esz) && pitch_ok(ldddt, d, esz) && pitch_ok(lddz, d, esz) && pitch_ok(ldbc, N, esz) &&
+                     pitch_ok(lddbc, N, esz),
+                 "selective_scan_bwd: row pitches must cover their rows (d = %d, Bm/Cm %d) and be multiples of 16 bytes", d, N);
+    HS_SUPPORTED(N == 16 || (aligned16(A_log) && aligned16(Bm) && aligned16(Cm) && aligned16(hck)),
+                 "selective_scan_bwd: A_log, Bm, Cm and hck must be 16-byte aligned for d_state %d", N);
+    HS_REQUIRE(ws_bytes >= hs_selective_scan_ws_bytes_n(B, L, d, N), "selective_scan_bwd: workspace of %lld bytes is too small",
                (long long)ws_bytes);
     const int nblk = ceil_div(d, 16);
     const long long rows = (long long)B * L;
     float* part_bc = (float*)ws;
-    float* part_p = part_bc + (long long)nblk * rows * 32;
-    const dim3 grid(nblk, B);
-    const int rgrid = grid_for(rows * 32 + (long long)d * 18);
+    float* part_p = part_bc + (long long)nblk * rows * 2 * N;
+    int sh = 0;
+    while ((1 << sh) < 2 * N) ++sh;
+    const int rgrid = grid_for(rows * 2 * N + (long long)d * (N + 2));
     if (dtype == HS_BF16) {
-        hipLaunchKernelGGL(selective_scan_bwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dout, lddo,
-                           (const bf16_t*)u, ldu, (const bf16_t*)dt, lddt, dt_bias, A_log, (const bf16_t*)Bm, (const bf16_t*)Cm,
-                           ldbc, D, (const bf16_t*)z, ldz, hck, (bf16_t*)du, lddu, (bf16_t*)ddt, ldddt, (bf16_t*)dz, lddz,
-                           part_bc, part_p, B, L, d);
+        HS_SCAN_DISPATCH(launch_scan_bwd, bf16_t, dout, lddo, u, ldu, dt, lddt, dt_bias, A_log, Bm, Cm, ldbc, D, z, ldz, hck, du,
+                         lddu, ddt, ldddt, dz, lddz, part_bc, part_p, B, L, d, (hipStream_t)stream);
         HS_LAUNCH_CHECK();
         hipLaunchKernelGGL(selective_scan_bwd_reduce_kernel<bf16_t>, dim3(rgrid), dim3(256), 0, (hipStream_t)stream, part_bc,
-                           part_p, nblk, rows, B, d, (bf16_t*)dBm, (bf16_t*)dCm, lddbc, dA_log, dD, ddt_bias);
+                           part_p, nblk, rows, B, d, N, sh, (bf16_t*)dBm, (bf16_t*)dCm, lddbc, dA_log, dD, ddt_bias);
     } else {
-        hipLaunchKernelGGL(selective_scan_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dout, lddo,
-                           (const float*)u, ldu, (const float*)dt, lddt, dt_bias, A_log, (const float*)Bm, (const float*)Cm, ldbc,
-                           D, (const float*)z, ldz, hck, (float*)du, lddu, (float*)ddt, ldddt, (float*)dz, lddz, part_bc, part_p,
-                           B, L, d);
+        HS_SCAN_DISPATCH(launch_scan_bwd, float, dout, lddo, u, ldu, dt, lddt, dt_bias, A_log, Bm, Cm, ldbc, D, z, ldz, hck, du,
+                         lddu, ddt, ldddt, dz, lddz, part_bc, part_p, B, L, d, (hipStream_t)stream);
         HS_LAUNCH_CHECK();
         hipLaunchKernelGGL(selective_scan_bwd_reduce_kernel<float>, dim3(rgrid), dim3(256), 0, (hipStream_t)stream, part_bc,
-                           part_p, nblk, rows, B, d, (float*)dBm, (float*)dCm, lddbc, dA_log, dD, ddt_bias);
+                           part_p, nblk, rows, B, d, N, sh, (float*)dBm, (float*)dCm, lddbc, dA_log, dD, ddt_bias);
     }
     HS_LAUNCH_CHECK();
     return HS_OK;
@@ -462,6 +636,31 @@ hs_status hs_add_token_bias_bwd(int32_t dtype, const void* dy, float* dv, int32_
     else
         hipLaunchKernelGGL(add_token_bias_bwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)dy, dv,
                            B, L, H);
+    HS_LAUNCH_CHECK();
+    return HS_OK;
+}
+
+hs_status hs_transpose_batched_f32(const float* src, float* dst, int32_t B, int32_t R, int32_t Cc, void* stream) {
+    HS_REQUIRE(src && dst && B > 0 && R > 0 && Cc > 0, "transpose_batched_f32: bad argument");
+    HS_SUPPORTED(B <= 65535 && ceil_div(R, 32) <= 65535, "transpose_batched_f32: B %d or R %d exceeds the grid limit", B, R);
+    hipLaunchKernelGGL(transpose_batched_kernel, dim3(ceil_div(Cc, 32), ceil_div(R, 32), B), dim3(256), 0, (hipStream_t)stream,
+                       src, dst, R, Cc);
+    HS_LAUNCH_CHECK();
+    return HS_OK;
+}
+hs_status hs_token_seq_assemble_fwd(const float* text, const float* img, const float* first, const float* last, const float* pe,
+                                    float* seq, int32_t B, int32_t P, int32_t H, void* stream) {
+    HS_REQUIRE(text && img && first && last && pe && seq && B > 0 && P > 0 && H > 0, "token_seq_assemble_fwd: bad argument");
+    hipLaunchKernelGGL(token_seq_assemble_kernel, dim3(grid_for((long long)B * (P + 3) * H)), dim3(256), 0, (hipStream_t)stream,
+                       text, img, first, last, pe, seq, B, P, H);
+    HS_LAUNCH_CHECK();
+    return HS_OK;
+}
+hs_status hs_token_seq_assemble_bwd(const float* dseq, float* dtext, float* dimg, float* dfirst, float* dlast, int32_t B,
+                                    int32_t P, int32_t H, void* stream) {
+    HS_REQUIRE(dseq && B > 0 && P > 0 && H > 0, "token_seq_assemble_bwd: bad argument");
+    hipLaunchKernelGGL(token_seq_assemble_bwd_kernel, dim3(grid_for((long long)B * (P + 3) * H)), dim3(256), 0,
+                       (hipStream_t)stream, dseq, dtext, dimg, dfirst, dlast, B, P, H);
     HS_LAUNCH_CHECK();
     return HS_OK;
 }

@@ -1,5 +1,6 @@
-"""Mamba block of the SSM fusion (reference modules/fusion_blocks.py:264-292 -> mamba_ssm.Mamba, d_state 16, d_conv 4).
-The four projections run through hamspine.functional.linear; the causal depthwise conv1d + SiLU and the selective scan
+"""Mamba block of the SSM fusion (reference modules/fusion_blocks.py:264-292 -> mamba_ssm.Mamba, d_state 16, d_conv 4) and of
+the multimodal Mamba blocks (reference ConNexT/models/block/len4mamba.py:74-79,138-143, d_state 128); the scan takes d_state
+in D_STATES.  The four projections run through hamspine.functional.linear; the causal depthwise conv1d + SiLU and the selective scan
 are one C call per direction (hs_causal_conv1d_* / hs_selective_scan_*, csrc/ssm.hip).  Activations stay in the compute
 dtype, the state and every sum are f32.  Column slices of the in_proj / x_proj outputs are read in place through their row
 pitch; the two splits below hand autograd one gradient per GEMM output instead of zero-padded slices."""
@@ -9,7 +10,8 @@ from torch.autograd import Function
 from . import _lib as L
 from . import rt
 
-D_STATE, D_CONV = 16, 4
+D_STATE, D_CONV = 16, 4                 # the defaults of mamba_ssm.Mamba
+D_STATES = (16, 32, 64, 128, 256)       # what hs_selective_scan_* takes
 
 
 def _pitched(t):
@@ -134,8 +136,8 @@ class CausalConv1dFn(Function):
 
 class SelectiveScanFn(Function):
     """out = (scan(u, softplus(dt + dt_bias), -exp(A_log), Bm, Cm) + D u) * silu(z).
-    u, dt, z: (B, L, d); bc: (B, L, 32) = [Bm | Cm]; A_log (d, 16), D, dt_bias (d,) f32.  u / dt / z / bc may be column
-    slices.  Saved for the backward: the inputs and the state after every chunk, (B, (L-1)//chunk, d, 16) f32."""
+    u, dt, z: (B, L, d); bc: (B, L, 2N) = [Bm | Cm]; A_log (d, N), D, dt_bias (d,) f32, N = d_state.  u / dt / z / bc may be
+    column slices.  Saved for the backward: the inputs and the state after every chunk, (B, (L-1)//chunk(N), d, N) f32."""
 
     @staticmethod
     def forward(ctx, u, dt, dt_bias, A_log, bc, D, z):
@@ -154,8 +156,9 @@ class SelectiveScanFn(Function):
         out = torch.empty((B, Lt, d), dtype=u.dtype, device=u.device)
         need = any(ctx.needs_input_grad)
         hck = None
-        if need and Lt > 0:
-            nck = (Lt - 1) // lib.hs_selective_scan_chunk_len()
+        chunk = lib.hs_selective_scan_chunk_len_n(N)
+        if need and Lt > 0 and chunk > 0:      # an unsupported d_state is refused by the call below
+            nck = (Lt - 1) // chunk
             hck = torch.empty((B, nck, d, N), dtype=torch.float32, device=u.device) if nck > 0 else None
         L.check(lib.hs_selective_scan_fwd(rt.hs_dtype(u), rt.p(u), ldu, rt.p(dt), lddt, rt.p(dt_bias), rt.p(A_log), rt.p(bc),
                                           rt.p(bc, N * esz), ldbc, rt.p(D), rt.p(z), ldz, rt.p(out), d, rt.p(hck), B, Lt, d, N,
@@ -184,13 +187,67 @@ class SelectiveScanFn(Function):
         dA = rt.grad_buffer_like(A_log)
         dD = rt.grad_buffer_like(D)
         dbias = rt.grad_buffer_like(dt_bias)
-        wsb = lib.hs_selective_scan_ws_bytes(B, Lt, d)
+        wsb = lib.hs_selective_scan_ws_bytes_n(B, Lt, d, N)
         ws = rt.workspace(wsb, u.device)
         L.check(lib.hs_selective_scan_bwd(rt.hs_dtype(T), rt.p(dout), d, rt.p(u), ldu, rt.p(dt), lddt, rt.p(dt_bias), rt.p(A_log),
                                           rt.p(bc), rt.p(bc, N * esz), ldbc, rt.p(D), rt.p(z), ldz, rt.p(hck), rt.p(du), d,
                                           rt.p(ddt), d, rt.p(dbc), rt.p(dbc, N * esz), 2 * N, rt.p(dz), d, rt.p(dA), rt.p(dD),
                                           rt.p(dbias), rt.p(ws), ws.numel(), B, Lt, d, N, rt.stream()), "hs_selective_scan_bwd")
         return du, ddt, dbias, dA, dbc, dD, dz
+
+
+class TransposeBatchedFn(Function):
+    """(B, R, C) f32 -> (B, C, R) contiguous in one launch (the image feature (B, C, P) as (B, P, C) projection rows)"""
+
+    @staticmethod
+    def forward(ctx, x):
+        rt.need_gpu(x)
+        if x.dtype != torch.float32:
+            raise L.HamspineError(f"transpose_batched expects an f32 tensor, got {x.dtype}")
+        return TransposeBatchedFn._run(x.contiguous())
+
+    @staticmethod
+    def _run(x):
+        B, R, Cc = x.shape
+        o = torch.empty((B, Cc, R), dtype=torch.float32, device=x.device)
+        L.check(L.lib().hs_transpose_batched_f32(rt.p(x), rt.p(o), B, R, Cc, rt.stream()), "hs_transpose_batched_f32")
+        return o
+
+    @staticmethod
+    def backward(ctx, g):
+        return TransposeBatchedFn._run(_same(g, torch.float32))
+
+
+class TokenSeqAssembleFn(Function):
+    """[text (B, H); img (B, P, H); first (B, H); last (B, H)] + pe[:P + 3] -> (B, P + 3, H), f32, one launch per direction"""
+
+    @staticmethod
+    def forward(ctx, text, img, first, last, pe):
+        rt.need_gpu(text, img, first, last, pe)
+        ts = [t.contiguous() for t in (text, img, first, last, pe)]
+        if any(t.dtype != torch.float32 for t in ts):
+            raise L.HamspineError("token_seq_assemble expects f32 tensors")
+        text, img, first, last, pe = ts
+        B, P, H = img.shape
+        if text.shape != (B, H) or first.shape != (B, H) or last.shape != (B, H) or pe.shape[-1] != H or pe.numel() < (P + 3) * H:
+            raise L.HamspineError("token_seq_assemble: text / first / last (B, H), img (B, P, H) and pe (>= P + 3, H) must agree")
+        seq = torch.empty((B, P + 3, H), dtype=torch.float32, device=img.device)
+        L.check(L.lib().hs_token_seq_assemble_fwd(rt.p(text), rt.p(img), rt.p(first), rt.p(last), rt.p(pe), rt.p(seq), B, P, H,
+                                                  rt.stream()), "hs_token_seq_assemble_fwd")
+        ctx.meta = (B, P, H)
+        return seq
+
+    @staticmethod
+    def backward(ctx, g):
+        B, P, H = ctx.meta
+        g = _same(g, torch.float32)
+        need = ctx.needs_input_grad
+        outs = [torch.empty(shape, dtype=torch.float32, device=g.device) if n else None
+                for n, shape in zip(need[:4], ((B, H), (B, P, H), (B, H), (B, H)))]
+        if any(o is not None for o in outs):
+            L.check(L.lib().hs_token_seq_assemble_bwd(rt.p(g), *[rt.p(o) for o in outs], B, P, H, rt.stream()),
+                    "hs_token_seq_assemble_bwd")
+        return (*outs, None)
 
 
 def split_views(x, a):
@@ -211,3 +268,11 @@ def causal_conv1d(x, weight, bias):
 
 def selective_scan(u, dt, dt_bias, A_log, bc, D, z):
     return SelectiveScanFn.apply(u, dt, dt_bias, A_log, bc, D, z)
+
+
+def transpose_batched(x):
+    return TransposeBatchedFn.apply(x)
+
+
+def token_seq_assemble(text, img, first, last, pe):
+    return TokenSeqAssembleFn.apply(text, img, first, last, pe)

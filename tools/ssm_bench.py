@@ -4,9 +4,14 @@ reference's configs/ham/ham_fusion_ssm_v1.yml: B 64, L 49 image tokens, hidden 2
 Each C entry point is timed on its own with device events around --launches back-to-back launches, after --warmup
 launches, --repeats times; the table gives the median and the spread.  "bytes" counts every operand once in and every
 result once out (workspaces and recomputation not counted); "HBM %" is bytes / time over the 8.0 TB/s peak.  The module
-rows time forward, and forward + backward, of SSMFusionModule(768, 256) with 32 text tokens.
+rows time forward, and forward + backward, of SSMFusionModule(768, 256) with 32 text tokens (d_state 16 only).
 
-    python tools/ssm_bench.py [--dtype bf16|f32] [--launches 200] [--warmup 20] [--repeats 5]
+--d-state N times the kernels at another state size (16, 32, 64, 128, 256); --batch 16 --tokens 52 --d-state 128 is the shape
+of the multimodal Mamba blocks (reference ConNexT/models/block/len4mamba.py).  --len4mamba adds forward + backward of
+MultimodalMambaWithKANAttention with the reference's defaults (768 / 640 / 3584 / 256, 4 heads, 49 image tokens) at --batch, and
+the number of kernel launches of one such step as the profiler counts them.
+
+    python tools/ssm_bench.py [--dtype bf16|f32] [--d-state 16] [--len4mamba] [--launches 200] [--warmup 20] [--repeats 5]
 """
 import argparse
 import os
@@ -27,6 +32,8 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--tokens", type=int, default=49)
     ap.add_argument("--hidden", type=int, default=256)
+    ap.add_argument("--d-state", type=int, default=16)
+    ap.add_argument("--len4mamba", action="store_true")
     a = ap.parse_args()
 
     import torch
@@ -41,7 +48,7 @@ def main():
     hdt = rt.hs_dtype(T)
     esz = 2 if a.dtype == "bf16" else 4
     B, Lt, H = a.batch, a.tokens, a.hidden
-    d, N = 2 * H, 16
+    d, N = 2 * H, a.d_state
     rows = B * Lt
     dev = "cuda"
     g = torch.Generator().manual_seed(0)
@@ -49,18 +56,18 @@ def main():
     def rnd(*shape, scale=1.0):
         return (scale * torch.randn(*shape, generator=g)).to(dev, T)
     from hamspine.nn import Mamba
-    blk = Mamba(H).to(dev)
+    blk = Mamba(H, d_state=N).to(dev)
     xz, u, dt, bc, dout = rnd(B, Lt, 2 * d), rnd(B, Lt, d), rnd(B, Lt, d, scale=0.5), rnd(B, Lt, 2 * N), rnd(B, Lt, d)
     cw, cb = blk.conv1d.weight.detach(), blk.conv1d.bias.detach()
     A_log, D, dtb = blk.A_log.detach(), blk.D.detach(), blk.dt_proj.bias.detach()
     y = torch.empty(B, Lt, d, device=dev, dtype=T)
     out = torch.empty_like(y)
-    nck = (Lt - 1) // lib.hs_selective_scan_chunk_len()
+    nck = (Lt - 1) // lib.hs_selective_scan_chunk_len_n(N)
     hck = torch.empty(B, max(nck, 1), d, N, device=dev)
     du, ddt, dz, dxs = (torch.empty_like(y) for _ in range(4))
     dbc = torch.empty(B, Lt, 2 * N, device=dev, dtype=T)
     dA, dD, ddtb, dcw, dcb = (torch.empty_like(t) for t in (A_log, D, dtb, cw, cb))
-    ws = torch.empty(max(lib.hs_selective_scan_ws_bytes(B, Lt, d), lib.hs_causal_conv1d_ws_bytes(B, d)), dtype=torch.uint8,
+    ws = torch.empty(max(lib.hs_selective_scan_ws_bytes_n(B, Lt, d, N), lib.hs_causal_conv1d_ws_bytes(B, d)), dtype=torch.uint8,
                      device=dev)
     p, st = rt.p, rt.stream()
     z_off = d * esz
@@ -115,25 +122,44 @@ def main():
         bw = nbytes / (med * 1e-6)
         print(f"{name:<36} {med:>9.2f} {lo:>8.2f} {hi:>8.2f} {nbytes:>12d} {bw / 1e9:>8.1f} {100 * bw / HBM_PEAK:>6.2f}")
 
-    from modules.fusion_blocks import SSMFusionModule
-    torch.manual_seed(0)
-    m = SSMFusionModule(768, H).to(dev).train()
-    img = rnd(B, Lt, H).requires_grad_(True)
-    txt = rnd(B, 32, 768).requires_grad_(True)
-    w = torch.randn(B, H, generator=g).to(dev)
+    def module_rows(title, m, leaves, grad_out):
+        def fwd():
+            with torch.no_grad():
+                m(*leaves)
 
-    def mod_fwd():
-        with torch.no_grad():
-            m(img, txt)
+        def fwd_bwd():
+            m(*leaves).backward(grad_out)
+            for q in m.parameters():
+                q.grad = None
+            for t in leaves:
+                t.grad = None
+        for name, fn in ((title + " forward (no_grad)", fwd), (title + " forward + backward", fwd_bwd)):
+            med, lo, hi = timed(fn)
+            print(f"{name:<36} {med:>9.2f} {lo:>8.2f} {hi:>8.2f}")
+        return fwd_bwd
 
-    def mod_fwd_bwd():
-        m(img, txt).backward(w)
-        for q in m.parameters():
-            q.grad = None
-        img.grad = txt.grad = None
-    for name, fn in (("SSMFusionModule forward (no_grad)", mod_fwd), ("SSMFusionModule forward + backward", mod_fwd_bwd)):
-        med, lo, hi = timed(fn)
-        print(f"{name:<36} {med:>9.2f} {lo:>8.2f} {hi:>8.2f}")
+    if N == 16:
+        from modules.fusion_blocks import SSMFusionModule
+        torch.manual_seed(0)
+        m = SSMFusionModule(768, H).to(dev).train()
+        module_rows("SSMFusionModule", m, [rnd(B, Lt, H).requires_grad_(True), rnd(B, 32, 768).requires_grad_(True)],
+                    torch.randn(B, H, generator=g).to(dev))
+
+    if a.len4mamba:
+        from torch.profiler import ProfilerActivity, profile
+
+        from ConNexT.models.block.len4mamba import MultimodalMambaWithKANAttention
+        torch.manual_seed(0)
+        m = MultimodalMambaWithKANAttention().to(dev).train()
+        leaves = [torch.randn(*shape, generator=g).to(dev).requires_grad_(True)
+                  for shape in ((B, 768), (B, 640, 49), (B, 3584), (B, 3584))]
+        step = module_rows("MultimodalMambaWithKANAttention", m, leaves, torch.randn(B, 52, 256, generator=g).to(dev))
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            step()
+            torch.cuda.synchronize()
+        kernels = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+        print(f"MultimodalMambaWithKANAttention forward + backward at B {B}: {len(kernels)} device launches "
+              f"(kernels and copies), {sum(e.device_time for e in kernels):.1f} us of device time")
 
 
 if __name__ == "__main__":
