@@ -473,6 +473,37 @@ int32_t hs_selective_scan_chunk_len_n(int32_t N);
 /* Workspace of hs_selective_scan_bwd at d_state N (reference ConNexT/models/block/len4mamba.py:74-79,138-143): per-block
    partials [ceil(d/16)][B*L][2N] and per-batch partials [B][d][N + 2], f32; -1 for an unsupported N. */
 int64_t hs_selective_scan_ws_bytes_n(int32_t B, int32_t L, int32_t d, int32_t N);
+/* The scan above without the gate, N = 8 (reference ConNexT/models/block/mamba_vision.py:1622-1631: selective_scan_fn with
+   z=None, d_state 8 from 1719-1723): hs_selective_scan_fwd / _bwd with N = 8 take z = NULL (and dz = NULL; ldz, lddz are
+   ignored), out_t = y_t, and there is no dz.  8 lanes per (batch, channel) pair, 32 channels per block.  N = 8 with a gate,
+   and z = NULL at any other N, return HS_ERR_UNSUPPORTED before any launch.  out may be a column slice of a wider buffer
+   (pitch ldo).  The gate is a compile-time property of a kernel, so its queries are apart: the two below answer for the
+   gate-less instantiations (N = 8: 16 steps between saved states; per-block partials [ceil(d/32)][B*L][16] and per-batch
+   partials [B][d][10], f32) and return -1 for any other N, as the _n queries above do for N = 8. */
+int32_t hs_selective_scan_chunk_len_nogate(int32_t N);
+int64_t hs_selective_scan_ws_bytes_nogate(int32_t B, int32_t L, int32_t d, int32_t N);
+/* y[b][t][c] = silu(bias[c] + w[c][0] x[b][t-1][c] + w[c][1] x[b][t][c] + w[c][2] x[b][t+1][c]), x = 0 outside [0, L); bias
+   may be NULL (reference ConNexT/models/block/mamba_vision.py:1615-1616: F.silu(F.conv1d(..., padding='same', groups=d)) with
+   the bias-less (d, 1, 3) weights of 1588-1603).  x and y carry their own row pitch, so both halves of the in_proj output are
+   read in place and y may be a column slice of the buffer out_proj reads (the torch.cat of 1633). */
+hs_status hs_conv1d_same_silu_fwd(int32_t dtype, const void* x, int32_t ldx, const float* weight, const float* bias, void* y,
+                                  int32_t ldy, int32_t B, int32_t L, int32_t d, int32_t k, void* stream);
+/* dx, dweight [d][3] and, when bias is given, dbias [d] of the above (reference ConNexT/models/block/mamba_vision.py:1615-1616);
+   bias and dbias are both NULL or both given; the pre-activation is recomputed from x.  ws: hs_conv1d_same_silu_ws_bytes(B, d)
+   (per-batch partials, summed over b in order). */
+hs_status hs_conv1d_same_silu_bwd(int32_t dtype, const void* dy, int32_t lddy, const void* x, int32_t ldx, const float* weight,
+                                  const float* bias, void* dx, int32_t lddx, float* dweight, float* dbias, void* ws,
+                                  int64_t ws_bytes, int32_t B, int32_t L, int32_t d, int32_t k, void* stream);
+int64_t hs_conv1d_same_silu_ws_bytes(int32_t B, int32_t d);
+/* map (B, C, H, W) f32 -> tokens (B nWh nWw, ws ws, C) of `dtype`, nWh = ceil(H / ws), nWw = ceil(W / ws): the zero padding to
+   the right and bottom and window_partition of reference ConNexT/models/block/mamba_vision.py:1301-1314,1813-1820, with the
+   cast to the compute dtype.  Also the backward of hs_window_reverse. */
+hs_status hs_window_partition(int32_t dtype, const float* map, void* tokens, int32_t B, int32_t C, int32_t H, int32_t W, int32_t ws,
+                              void* stream);
+/* tokens (B nWh nWw, ws ws, C) of `dtype` -> map (B, C, H, W) f32, dropping the tokens of padded positions: window_reverse and
+   the crop of reference ConNexT/models/block/mamba_vision.py:1317-1330,1825-1827.  Also the backward of hs_window_partition. */
+hs_status hs_window_reverse(int32_t dtype, const void* tokens, float* map, int32_t B, int32_t C, int32_t H, int32_t W, int32_t ws,
+                            void* stream);
 /* out[b][t][:] = x[b][t][:] + v[b][:] (v f32): the pooled text feature added to every image token
    (reference modules/fusion_blocks.py:264-292, `image_tokens + txt_feat`). */
 hs_status hs_add_token_bias_fwd(int32_t dtype, const void* x, const float* v, void* out, int32_t B, int32_t L, int32_t H,

@@ -272,6 +272,16 @@ def _declare(l):
     l.hs_selective_scan_chunk_len_n.restype = i32
     l.hs_selective_scan_ws_bytes_n.argtypes = [i32, i32, i32, i32]
     l.hs_selective_scan_ws_bytes_n.restype = i64
+    l.hs_selective_scan_chunk_len_nogate.argtypes = [i32]
+    l.hs_selective_scan_chunk_len_nogate.restype = i32
+    l.hs_selective_scan_ws_bytes_nogate.argtypes = [i32, i32, i32, i32]
+    l.hs_selective_scan_ws_bytes_nogate.restype = i64
+    l.hs_conv1d_same_silu_fwd.argtypes = [i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    l.hs_conv1d_same_silu_bwd.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, vp]
+    l.hs_conv1d_same_silu_ws_bytes.argtypes = [i32, i32]
+    l.hs_conv1d_same_silu_ws_bytes.restype = i64
+    l.hs_window_partition.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
+    l.hs_window_reverse.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
     l.hs_add_token_bias_fwd.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp]
     l.hs_add_token_bias_bwd.argtypes = [i32, vp, vp, i32, i32, i32, vp]
     l.hs_token_seq_assemble_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]

@@ -12,6 +12,17 @@ from .. import ssm
 from .layers import Linear
 
 
+def low_rank_weights(wx, wdt, R):
+    """x_proj / dt_proj weights with the dt rank R padded to a multiple of 8 by zero rows / columns: the bf16 GEMM moves
+    16-byte chunks, so a K or a row pitch of 3 (d_model 40) would not be accepted.  The zero rows of x_proj make the
+    padding columns of its output exact zeros, which is the zero padding the dt_proj GEMM's K tail needs."""
+    Rp = -(-R // 8) * 8
+    if Rp != R:
+        wx = torch.cat([wx[:R], wx.new_zeros(Rp - R, wx.shape[1]), wx[R:]], dim=0)
+        wdt = torch.nn.functional.pad(wdt, (0, Rp - R))
+    return Rp, wx, wdt
+
+
 class Mamba(nn.Module):
     def __init__(self, d_model, d_state=ssm.D_STATE, d_conv=ssm.D_CONV, expand=2, dt_rank="auto", dt_min=1e-3, dt_max=1e-1,
                  dt_init_floor=1e-4):
@@ -41,16 +52,7 @@ class Mamba(nn.Module):
         self.out_proj = Linear(d, d_model, bias=False)
 
     def _low_rank_weights(self):
-        """x_proj / dt_proj weights with the dt rank padded to a multiple of 8 by zero rows / columns: the bf16 GEMM moves
-        16-byte chunks, so a K or a row pitch of 3 (d_model 40) would not be accepted.  The zero rows of x_proj make the
-        padding columns of its output exact zeros, which is the zero padding the dt_proj GEMM's K tail needs."""
-        R, d = self.dt_rank, self.d_inner
-        Rp = -(-R // 8) * 8
-        wx, wdt = self.x_proj.weight, self.dt_proj.weight
-        if Rp != R:
-            wx = torch.cat([wx[:R], wx.new_zeros(Rp - R, d), wx[R:]], dim=0)
-            wdt = torch.nn.functional.pad(wdt, (0, Rp - R))
-        return Rp, wx, wdt
+        return low_rank_weights(self.x_proj.weight, self.dt_proj.weight, self.dt_rank)
 
     def forward(self, x, mean_tokens=False, residual=None, out_dtype=None):
         """x (B, L, d_model) in the compute dtype -> (B, L, d_model); with mean_tokens the f32 mean over L, (B, d_model),
