@@ -153,6 +153,15 @@ typedef struct hs_gemm_params {
        partial_rows = hs_gemm_bnb_finish_rows(p) and sums_done = 1 (apply pass only): one launch per BatchNorm less on the
        stream (reference: torch's batch_norm_backward reduce + elementwise kernels). */
     const struct hs_bn_bwd_params* bnb_finish;
+    /* optional (plain bf16 GEMMs, batch 1): row counts that live in DEVICE memory -- the BERT tower on its valid tokens only
+       (hs_bert_desc.pack_rows).  The host never reads them: the grid, the tile shape and every buffer stay those of the padded
+       M / K, and the kernels clamp what they read.  NULL = off.
+         m_rows    the tokens are the rows of D: only rows < *m_rows are needed; tiles that start at or behind it are skipped
+                   (the tile that holds row *m_rows is computed whole; rows >= *m_rows of D are then unspecified)
+         drop_rows [M] int32: the dropout draw of output row m is the one of row drop_rows[m] (the padded position of a packed
+                   row), so a packed and a padded run apply the same mask */
+    const int32_t* m_rows;
+    const int32_t* drop_rows;
 } hs_gemm_params;
 
 hs_status hs_gemm(const hs_gemm_params* p, void* stream);
@@ -823,8 +832,24 @@ typedef struct hs_bert_desc {
     float* dbeta;
     int32_t n_layers;
     hs_bert_layer_desc layers[HS_BERT_MAX_LAYERS];   /* attention_mask / seed fields are overridden per call           */
+    /* 1: compute only the tokens whose attention_mask is non-zero (bf16, head dim 64, L <= 128, a mask must be given; anything
+       else is an error -- the caller decides).  A kernel makes the row map on the device (cu[B + 1] = exclusive prefix sum of
+       the valid counts, row_of[t] = padded row b*L + l of packed row t, T = cu[B]) and the host never reads it back: every
+       grid and every buffer stays sized for B*L rows, packed rows occupy the first T rows of the same buffers.  Valid tokens
+       keep their order, so holes in a mask are handled like padding; a sequence without valid tokens contributes no rows.
+       last_hidden_state is written in the padded [B][L][hidden] layout with ZEROS at masked positions, and the backward
+       ignores the cotangent there.  Kernels that sum over tokens (weight / bias / LayerNorm gradients) walk the PADDED positions
+       and leave the masked ones out, where the padded tower adds exact zeros: for right-padded masks every valid hidden state
+       and every gradient is bitwise what the padded tower computes, dropout draws included.  With holes in a mask the
+       attention sums over keys round differently and the attention-probability draws differ (their flat index counts keys
+       in packed order). */
+    int32_t pack_rows;
 } hs_bert_desc;
-/* out_offset: byte offset of last_hidden_state ([B][L][hidden], compute dtype) inside `saved`. */
+/* 1 when the switches the library has latched (HAMSPINE_WGRAD_NT / hs_set_wgrad_nt, HAMSPINE_FUSED_ATTENTION) leave pack_rows
+   the kernels it needs, 0 when a caller must keep the padded tower. */
+int32_t hs_bert_pack_rows_available(void);
+/* out_offset: byte offset of last_hidden_state ([B][L][hidden], compute dtype) inside `saved`; with pack_rows it is the ONLY
+   way to find the output (the row map and the padded output sit in front of the other buffers). */
 hs_status hs_bert_query(const hs_bert_desc* d, int64_t* saved_bytes, int64_t* ws_bytes, int64_t* out_offset);
 hs_status hs_bert_fwd(const hs_bert_desc* d, const int64_t* ids, const int64_t* mask, void* saved, int64_t saved_bytes,
                       void* ws, int64_t ws_bytes, void* stream);

@@ -86,11 +86,13 @@ class ImageEncoder(nn.Module):
 
 
 class TextEncoder(nn.Module):
-    """BERT tower returning token features (B, L, hidden) (reference encoder.py:112-134)."""
+    """BERT tower returning token features (B, L, hidden) (reference encoder.py:112-134).
 
-    def __init__(self, model_path="bert-base-uncased", feature_dim=768):
+    skip_padded_rows: the consumer key-masks the text tokens, so the tower may leave masked positions uncomputed (zeros)."""
+
+    def __init__(self, model_path="bert-base-uncased", feature_dim=768, skip_padded_rows=False):
         super().__init__()
-        self.model = BertModel.from_pretrained(model_path)
+        self.model = BertModel.from_pretrained(model_path, skip_padded_rows=skip_padded_rows)
 
     def forward(self, input_ids, attention_mask):
         return self.model(input_ids=input_ids, attention_mask=attention_mask).last_hidden_state

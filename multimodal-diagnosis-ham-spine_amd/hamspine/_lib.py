@@ -57,6 +57,7 @@ class GemmParams(C.Structure):
         ("bn_finish", vp),
         ("bnb_y", vp),
         ("bnb_finish", vp),
+        ("m_rows", vp), ("drop_rows", vp),
     ]
 
 
@@ -150,6 +151,7 @@ class BertDesc(C.Structure):
         ("word", vp), ("pos", vp), ("type0", vp), ("gamma", vp), ("beta", vp),
         ("dword", vp), ("dpos", vp), ("dtype0", vp), ("dgamma", vp), ("dbeta", vp),
         ("n_layers", i32), ("layers", BertLayerDesc * BERT_MAX_LAYERS),
+        ("pack_rows", i32),
     ]
 
 
@@ -304,6 +306,8 @@ def _declare(l):
     l.hs_measure_build.restype = i32
     l.hs_set_wgrad_nt.argtypes = [i32]
     l.hs_set_wgrad_nt.restype = None
+    l.hs_bert_pack_rows_available.argtypes = []
+    l.hs_bert_pack_rows_available.restype = i32
     l.hs_dwconv_ws_bytes.argtypes = [i32] * 5
     l.hs_dwconv_ws_bytes.restype = i64
     l.hs_dwconv_fwd.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp]

@@ -27,6 +27,17 @@ __device__ __forceinline__ void attn_drop4(unsigned long long seed, unsigned lon
     }
 }
 
+// Packed rows (cu != NULL; the BERT tower on its valid tokens, hs_bert_desc.pack_rows): batch b owns rows [cu[b], cu[b + 1]) of ONE
+// [tokens][ld] matrix instead of L rows at b * bs, and its query / key count is that difference.  What is read from the device
+// is clamped so that no address leaves the padded allocation: 0 <= len <= Lmax and first + len <= nb * Lmax.
+__device__ __forceinline__ void packed_span(const int* cu, int b, int nb, int Lmax, int& first, int& len) {
+    const int total = nb * Lmax;
+    const int c0 = min(max(__builtin_amdgcn_readfirstlane(cu[b]), 0), total);
+    const int c1 = __builtin_amdgcn_readfirstlane(cu[b + 1]);
+    len = min(min(max(c1 - c0, 0), Lmax), total - c0);
+    first = c0;
+}
+
 struct AttnFusedArgs {
     const char* q;
     const char* k;
@@ -43,6 +54,7 @@ struct AttnFusedArgs {
     unsigned thresh;
     float inv_keep;
     unsigned long long seed;
+    const int* cu;                    // [B + 1] packed-row offsets or NULL (then key_mask is not used: every key below the length is valid)
 };
 
 // HD: head dimension (64: BERT; 32: the fusion modules' nn.MultiheadAttention(256, 8), reference modules/fusion_blocks.py:18-40,
@@ -68,8 +80,18 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
     const int bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
     const int q0 = blockIdx.y * LMAX;                       // first query row of this chunk
 
-    const long long qo = (long long)b * a.q_bs + (long long)h * HD, ko = (long long)b * a.k_bs + (long long)h * HD;
-    const long long vo = (long long)b * a.v_bs + (long long)h * HD;
+    // P / Pd rows and the dropout index keep the padded a.Lq / a.Lk strides in packed mode; Lq / Lk bound loads, scores and stores
+    int Lq = a.Lq, Lk = a.Lk;
+    long long qo = (long long)b * a.q_bs + (long long)h * HD, ko = (long long)b * a.k_bs + (long long)h * HD;
+    long long vo = (long long)b * a.v_bs + (long long)h * HD, oo = (long long)b * a.o_bs + (long long)h * HD;
+    if (a.cu) {
+        int first, len;
+        packed_span(a.cu, b, gridDim.x / a.H, a.Lq, first, len);
+        if (q0 >= len) return;                              // (workgroup-uniform, before any barrier; an empty sequence does nothing)
+        Lq = Lk = len;
+        qo = (long long)first * a.q_ld + (long long)h * HD; ko = (long long)first * a.k_ld + (long long)h * HD;
+        vo = (long long)first * a.v_ld + (long long)h * HD; oo = (long long)first * a.o_ld + (long long)h * HD;
+    }
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(a.q + qo * 2, (unsigned)min(a.q_bytes - (unsigned long long)qo * 2, 0x7fffff00ull));
     const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.k + ko * 2, (unsigned)min(a.k_bytes - (unsigned long long)ko * 2, 0x7fffff00ull));
     const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.v + vo * 2, (unsigned)min(a.v_bytes - (unsigned long long)vo * 2, 0x7fffff00ull));
@@ -80,7 +102,7 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
         const int s = (wave * NP + i) * 64 + lane;          // 16-byte slot of the query tile
         const int r = s / CPR, pc = s % CPR;
         const int kl = (pc ^ kc_swz<CPR>(r)) * 8;
-        const unsigned offq = q0 + r < a.Lq ? (unsigned)(((q0 + r) * a.q_ld + kl) * 2) : kOOB;
+        const unsigned offq = q0 + r < Lq ? (unsigned)(((q0 + r) * a.q_ld + kl) * 2) : kOOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, (__attribute__((address_space(3))) void*)((lds_char*)Qs + (wave * NP + i) * 1024), 16, offq, 0, 0, 0);
     }
 #pragma unroll
@@ -89,13 +111,13 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
         {   // K-contiguous tile: row = s / CPR, physical chunk = s % CPR holds logical chunk pc ^ kc_swz(row)
             const int r = s / CPR, pc = s % CPR;
             const int kl = (pc ^ kc_swz<CPR>(r)) * 8;
-            const unsigned offk = r < a.Lk ? (unsigned)((r * a.k_ld + kl) * 2) : kOOB;
+            const unsigned offk = r < Lk ? (unsigned)((r * a.k_ld + kl) * 2) : kOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)((lds_char*)Ks + (wave * NPK + i) * 1024), 16, offk, 0, 0, 0);
         }
         {   // key-major V tile [key][HD]: key = s / CPR, physical chunk s % CPR holds logical chunk rc_logical_chunk
             const int key = s / (HD / 8), pcc = s % (HD / 8);
             const int col = rc_logical_chunk<HD>(key, pcc) * 8;
-            const unsigned offv = key < a.Lk ? (unsigned)((key * a.v_ld + col) * 2) : kOOB;
+            const unsigned offv = key < Lk ? (unsigned)((key * a.v_ld + col) * 2) : kOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)((lds_char*)Vs + (wave * NPK + i) * 1024), 16, offv, 0, 0, 0);
         }
     }
@@ -123,14 +145,14 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
     }
 
     // ---- softmax over the LK keys of each row; lane holds keys 16 j + 4 g + e of row 16 FM wave + 16 i + l15 ------
-    const long long* mk = a.key_mask ? a.key_mask + (long long)b * a.Lk : nullptr;
+    const long long* mk = (a.key_mask && !a.cu) ? a.key_mask + (long long)b * a.Lk : nullptr;
     bool dead[FN][4];
 #pragma unroll
     for (int j = 0; j < FN; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int key = j * 16 + 4 * g + e;
-            dead[j][e] = key >= a.Lk || (mk && key < a.Lk && mk[key] == 0);
+            dead[j][e] = key >= Lk || (mk && key < Lk && mk[key] == 0);
         }
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
@@ -142,7 +164,7 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
             for (int e = 0; e < 4; ++e) {
                 const int key = j * 16 + 4 * g + e;
                 float s = acc[i][j][e] * a.scale;
-                if (dead[j][e]) s = key < a.Lk ? -3.0e38f : -INFINITY;   // masked keys as the unfused softmax, padding never counts
+                if (dead[j][e]) s = key < Lk ? -3.0e38f : -INFINITY;   // masked keys as the unfused softmax, padding never counts
                 acc[i][j][e] = s;
                 mx = fmaxf(mx, s);
             }
@@ -166,16 +188,16 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
             const int key0 = j * 16 + 4 * g;
             float p[4], pd[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) p[e] = (key0 + e < a.Lk) ? acc[i][j][e] * inv : 0.f;
+            for (int e = 0; e < 4; ++e) p[e] = (key0 + e < Lk) ? acc[i][j][e] * inv : 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) pd[e] = p[e];
-            if (a.thresh && key0 < a.Lk) {
+            if (a.thresh && key0 < Lk) {
                 float sc[4];
                 attn_drop4(a.seed, (unsigned long long)prow * a.Lk + key0, a.thresh, a.inv_keep, sc);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) pd[e] *= sc[e];
             }
-            if (qrow < a.Lq && key0 < a.ldP) {
+            if (qrow < Lq && key0 < a.ldP) {
                 bf16_t* dst = (bf16_t*)a.P + prow * a.ldP + key0;
                 *(bf16x4*)dst = bf16x4{(bf16_t)p[0], (bf16_t)p[1], (bf16_t)p[2], (bf16_t)p[3]};
                 if (a.Pd) {
@@ -221,8 +243,8 @@ __global__ __launch_bounds__(256) void attn_fwd_fused_kernel(const AttnFusedArgs
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
         const int qrow = q0 + wave * 16 * FM + i * 16 + l15;
-        if (qrow >= a.Lq) continue;
-        bf16_t* orow = (bf16_t*)a.o + (long long)b * a.o_bs + (long long)qrow * a.o_ld + (long long)h * HD;
+        if (qrow >= Lq) continue;
+        bf16_t* orow = (bf16_t*)a.o + oo + (long long)qrow * a.o_ld;
 #pragma unroll
         for (int jn = 0; jn < FO; ++jn) {
             const f32x4 v = oacc[i][jn];
@@ -253,6 +275,7 @@ struct AttnFusedBwdArgs {
     unsigned thresh;
     float inv_keep;
     unsigned long long seed;
+    const int* cu;                    // [B + 1] packed-row offsets or NULL, as AttnFusedArgs.cu (only the <= 128-row kernel reads it)
 };
 
 __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(const AttnFusedBwdArgs a) {
@@ -272,8 +295,17 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(const AttnFusedBwdA
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, l15 = lane & 15;
     const int bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H;
-    const long long qo = (long long)b * a.q_bs + (long long)h * HD, ko = (long long)b * a.k_bs + (long long)h * HD;
-    const long long vo = (long long)b * a.v_bs + (long long)h * HD, oo = (long long)b * a.o_bs + (long long)h * HD;
+    int Lq = a.Lq, Lk = a.Lk;        // packed mode: P rows and the dropout index keep the padded a.Lq / a.Lk strides
+    long long qo = (long long)b * a.q_bs + (long long)h * HD, ko = (long long)b * a.k_bs + (long long)h * HD;
+    long long vo = (long long)b * a.v_bs + (long long)h * HD, oo = (long long)b * a.o_bs + (long long)h * HD;
+    if (a.cu) {
+        int first, len;
+        packed_span(a.cu, b, gridDim.x / a.H, a.Lq, first, len);
+        if (len <= 0) return;                               // (workgroup-uniform, before any barrier)
+        Lq = Lk = len;
+        qo = (long long)first * a.q_ld + (long long)h * HD; ko = (long long)first * a.k_ld + (long long)h * HD;
+        vo = (long long)first * a.v_ld + (long long)h * HD; oo = (long long)first * a.o_ld + (long long)h * HD;
+    }
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(a.q + qo * 2, (unsigned)min(a.q_bytes - (unsigned long long)qo * 2, 0x7fffff00ull));
     const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.k + ko * 2, (unsigned)min(a.k_bytes - (unsigned long long)ko * 2, 0x7fffff00ull));
     const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.v + vo * 2, (unsigned)min(a.v_bytes - (unsigned long long)vo * 2, 0x7fffff00ull));
@@ -286,17 +318,17 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(const AttnFusedBwdA
         {   // k-contiguous tiles
             const int r = s / CPR, pc = s % CPR;
             const int kl = (pc ^ ((r / 2) % CPR)) * 8;
-            const unsigned offv = r < a.Lk ? (unsigned)((r * a.v_ld + kl) * 2) : kOOB;
-            const unsigned offo = r < a.Lq ? (unsigned)((r * a.o_ld + kl) * 2) : kOOB;
+            const unsigned offv = r < Lk ? (unsigned)((r * a.v_ld + kl) * 2) : kOOB;
+            const unsigned offo = r < Lq ? (unsigned)((r * a.o_ld + kl) * 2) : kOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)((lds_char*)Vkc + slot), 16, offv, 0, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ro, (__attribute__((address_space(3))) void*)((lds_char*)Okc + slot), 16, offo, 0, 0, 0);
         }
         {   // key-major tiles
             const int row = s / (HD / 8), pcc = s % (HD / 8);
             const int col = rc_logical_chunk<HD>(row, pcc) * 8;
-            const unsigned offo = row < a.Lq ? (unsigned)((row * a.o_ld + col) * 2) : kOOB;
-            const unsigned offk = row < a.Lk ? (unsigned)((row * a.k_ld + col) * 2) : kOOB;
-            const unsigned offq = row < a.Lq ? (unsigned)((row * a.q_ld + col) * 2) : kOOB;
+            const unsigned offo = row < Lq ? (unsigned)((row * a.o_ld + col) * 2) : kOOB;
+            const unsigned offk = row < Lk ? (unsigned)((row * a.k_ld + col) * 2) : kOOB;
+            const unsigned offq = row < Lq ? (unsigned)((row * a.q_ld + col) * 2) : kOOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ro, (__attribute__((address_space(3))) void*)((lds_char*)Orc + slot), 16, offo, 0, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)((lds_char*)Krc + slot), 16, offk, 0, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, (__attribute__((address_space(3))) void*)((lds_char*)Qrc + slot), 16, offq, 0, 0, 0);
@@ -338,12 +370,12 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(const AttnFusedBwdA
             float sc[4] = {1.f, 1.f, 1.f, 1.f};
 #pragma unroll
             for (int e = 0; e < 4; ++e) pv[j][e] = 0.f;
-            if (qrow < a.Lq && key0 < a.ldP) {
+            if (qrow < Lq && key0 < a.ldP) {
                 const u32x2 raw = *(const u32x2*)((const bf16_t*)a.P + prow * a.ldP + key0);
                 pv[j][0] = __uint_as_float(raw[0] << 16); pv[j][1] = __uint_as_float(raw[0] & 0xffff0000u);
                 pv[j][2] = __uint_as_float(raw[1] << 16); pv[j][3] = __uint_as_float(raw[1] & 0xffff0000u);
             }
-            if (a.thresh && key0 < a.Lk) attn_drop4(a.seed, (unsigned long long)prow * a.Lk + key0, a.thresh, a.inv_keep, sc);
+            if (a.thresh && key0 < Lk) attn_drop4(a.seed, (unsigned long long)prow * a.Lk + key0, a.thresh, a.inv_keep, sc);
             float pd[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -394,8 +426,8 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(const AttnFusedBwdA
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
             const int qrow = wave * 32 + i * 16 + l15;
-            if (qrow >= a.Lq) continue;
-            bf16_t* row = (bf16_t*)a.dq + (long long)b * a.q_bs + (long long)qrow * a.q_ld + (long long)h * HD;
+            if (qrow >= Lq) continue;
+            bf16_t* row = (bf16_t*)a.dq + qo + (long long)qrow * a.q_ld;
 #pragma unroll
             for (int jn = 0; jn < FO; ++jn) {
                 const f32x4 v = qa[i][jn];
@@ -406,7 +438,7 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(const AttnFusedBwdA
     }
 
     // ---- C / D. transposed products over all 128 query rows: this wave's 32 keys x 64 head columns ---------------
-    auto transposed_product = [&](const char* rhs_rc, char* out, long long out_bs, int out_ld, float alpha) {
+    auto transposed_product = [&](const char* rhs_rc, char* out, long long out_off, int out_ld, float alpha) {
         f32x4 ta[FM][FO];
 #pragma unroll
         for (int i = 0; i < FM; ++i)
@@ -438,8 +470,8 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(const AttnFusedBwdA
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
             const int key = wave * 32 + i * 16 + l15;
-            if (key >= a.Lk) continue;
-            bf16_t* row = (bf16_t*)out + (long long)b * out_bs + (long long)key * out_ld + (long long)h * HD;
+            if (key >= Lk) continue;
+            bf16_t* row = (bf16_t*)out + out_off + (long long)key * out_ld;
 #pragma unroll
             for (int jn = 0; jn < FO; ++jn) {
                 const f32x4 v = ta[i][jn];
@@ -449,7 +481,7 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(const AttnFusedBwdA
         }
     };
     __syncthreads();                                   // every wave's Pd rows are in the transpose tile
-    transposed_product(Orc, a.dv, a.v_bs, a.v_ld, 1.f);            // dV = Pd^T dO
+    transposed_product(Orc, a.dv, vo, a.v_ld, 1.f);            // dV = Pd^T dO
     __syncthreads();                                   // all reads of Pd done
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
@@ -461,7 +493,7 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(const AttnFusedBwdA
         }
     }
     __syncthreads();
-    transposed_product(Qrc, a.dk, a.k_bs, a.k_ld, a.scale);        // dK = scale * dS^T Q
+    transposed_product(Qrc, a.dk, ko, a.k_ld, a.scale);        // dK = scale * dS^T Q
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1006,27 +1038,35 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_long_kernel(const AttnFuse
 }
 
 // host side: eligibility + launch.  Returns 1 when the fused kernel ran, 0 when the shape is not covered, < 0 on error.
+// cu: packed rows (see packed_span), or NULL.  The caller (bert_check in blocks.hip, hamspine.tower.bert_pack_supported) has checked that the shape is one the
+// packed kernels cover; a launch that cannot honour cu is an error, never the padded computation.
+bool fused_attention_enabled() {             // HAMSPINE_FUSED_ATTENTION=0: the unfused attention path (read once)
+    static const bool on = [] { const char* e = getenv("HAMSPINE_FUSED_ATTENTION"); return !(e && e[0] == '0'); }();
+    return on;
+}
+static bool packed_shape_ok(const hs_attn_desc& d) {
+    return d.dtype == HS_BF16 && d.hd == 64 && d.Lq == d.Lk && d.Lk <= 128 && d.q_bs == (long long)d.Lq * d.q_ld &&
+           d.k_bs == (long long)d.Lk * d.k_ld && d.v_bs == (long long)d.Lk * d.v_ld && d.o_bs == (long long)d.Lq * d.o_ld;
+}
 int attention_fwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, void* o, void* P, void* Pd,
-                        int ldP, hipStream_t s) {
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char* e = getenv("HAMSPINE_FUSED_ATTENTION");
-        enabled = (e && e[0] == '0') ? 0 : 1;
-    }
+                        int ldP, hipStream_t s, const int* cu) {
+    if (cu && !packed_shape_ok(d)) return -1;
+    const bool enabled = fused_attention_enabled();
     // head dim 64 (BERT) or 32 (the fusion modules' 8-head attention over 256 features), any number of queries (128-row
     // chunks on grid.y), at most 128 keys -- 512 at head dim 64 (257..512 keys: 64-row chunks)
     const bool wide = d.hd == 64 && d.Lk > 256;
-    if (!enabled || d.dtype != HS_BF16 || (d.hd != 64 && d.hd != 32) || d.Lq < 1 || d.Lq > (wide ? 64 : 128) * 65535 || d.Lk < 1 || d.Lk > (d.hd == 64 ? 512 : 128) || ldP % 4 != 0 || ldP < d.Lk) return 0;
+    if (!enabled || d.dtype != HS_BF16 || (d.hd != 64 && d.hd != 32) || d.Lq < 1 || d.Lq > (wide ? 64 : 128) * 65535 || d.Lk < 1 || d.Lk > (d.hd == 64 ? 512 : 128) || ldP % 4 != 0 || ldP < d.Lk) return cu ? -1 : 0;
     const long long strides[] = {d.q_bs, d.k_bs, d.v_bs, d.o_bs, d.q_ld, d.k_ld, d.v_ld, d.o_ld};
     for (long long x : strides)
-        if (x % 8 != 0) return 0;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || (((uintptr_t)o | (uintptr_t)P | (uintptr_t)Pd) & 7)) return 0;
+        if (x % 8 != 0) return cu ? -1 : 0;
+    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || (((uintptr_t)o | (uintptr_t)P | (uintptr_t)Pd) & 7)) return cu ? -1 : 0;
     auto span = [&](long long bs, int L, int ld) { return ((long long)(d.B - 1) * bs + (long long)(L - 1) * ld + (long long)d.H * d.hd) * 2; };
     if (span(d.q_bs, d.Lq, d.q_ld) >= 0x7fffff00ll || span(d.k_bs, d.Lk, d.k_ld) >= 0x7fffff00ll ||
         span(d.v_bs, d.Lk, d.v_ld) >= 0x7fffff00ll)
-        return 0;
+        return cu ? -1 : 0;
     AttnFusedArgs a;
     memset(&a, 0, sizeof(a));
+    a.cu = cu;
     a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.o = (char*)o;
     a.P = (char*)P; a.Pd = d.dropout_p > 0.f ? (char*)Pd : nullptr;
     a.key_mask = (const long long*)d.key_mask;
@@ -1062,28 +1102,27 @@ int attention_fwd_fused(const hs_attn_desc& d, const void* q, const void* k, con
 // scratch: f32 workspace of scratch_bytes, used beyond 128 keys for the dQ slab and the row terms (B*H*Lq*65 floats);
 // O: the forward output with dO's strides, or NULL (used beyond 128 keys only)
 int attention_bwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, const void* dO, void* dq, void* dk,
-                        void* dv, const void* P, int ldP, void* scratch, long long scratch_bytes, const void* O, hipStream_t s) {
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char* e = getenv("HAMSPINE_FUSED_ATTENTION");
-        enabled = (e && e[0] == '0') ? 0 : 1;
-    }
-    if (!enabled || d.dtype != HS_BF16 || (d.hd != 64 && d.hd != 32) || d.Lq < 1 || d.Lk < 1 || d.Lk > (d.hd == 64 ? 512 : 128) || ldP % 4 != 0 || ldP < d.Lk) return 0;
+                        void* dv, const void* P, int ldP, void* scratch, long long scratch_bytes, const void* O, hipStream_t s,
+                        const int* cu) {
+    if (cu && !packed_shape_ok(d)) return -1;
+    const bool enabled = fused_attention_enabled();
+    if (!enabled || d.dtype != HS_BF16 || (d.hd != 64 && d.hd != 32) || d.Lq < 1 || d.Lk < 1 || d.Lk > (d.hd == 64 ? 512 : 128) || ldP % 4 != 0 || ldP < d.Lk) return cu ? -1 : 0;
     const bool long_keys = d.Lk > 128;
     const long long rows = (long long)d.B * d.H * d.Lq;
     if (long_keys && (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < rows * (64 + 1) * 4)) return 0;
     const long long strides[] = {d.q_bs, d.k_bs, d.v_bs, d.o_bs, d.q_ld, d.k_ld, d.v_ld, d.o_ld};
     for (long long x : strides)
-        if (x % 8 != 0) return 0;
+        if (x % 8 != 0) return cu ? -1 : 0;
     if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dO) & 15) ||
         (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)P) & 7))
-        return 0;
+        return cu ? -1 : 0;
     auto span = [&](long long bs, int L, int ld) { return ((long long)(d.B - 1) * bs + (long long)(L - 1) * ld + (long long)d.H * d.hd) * 2; };
     const long long sq = span(d.q_bs, d.Lq, d.q_ld), sk = span(d.k_bs, d.Lk, d.k_ld), sv = span(d.v_bs, d.Lk, d.v_ld),
                     so = span(d.o_bs, d.Lq, d.o_ld);
-    if (sq >= 0x7fffff00ll || sk >= 0x7fffff00ll || sv >= 0x7fffff00ll || so >= 0x7fffff00ll) return 0;
+    if (sq >= 0x7fffff00ll || sk >= 0x7fffff00ll || sv >= 0x7fffff00ll || so >= 0x7fffff00ll) return cu ? -1 : 0;
     AttnFusedBwdArgs a;
     memset(&a, 0, sizeof(a));
+    a.cu = cu;
     a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.dO = (const char*)dO;
     a.dq = (char*)dq; a.dk = (char*)dk; a.dv = (char*)dv; a.P = (const char*)P;
     a.q_bs = d.q_bs; a.k_bs = d.k_bs; a.v_bs = d.v_bs; a.o_bs = d.o_bs;

@@ -32,10 +32,38 @@ struct GemmGroup;
 GemmGroup* gemm_group_open(hipStream_t s, long long slot);   // slot: any key that is stable across steps (its device table is cached)
 int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s);
 int gemm_group_flush(GemmGroup* g, hipStream_t s);
+bool fused_attention_enabled();
 int attention_bwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, const void* dO, void* dq, void* dk,
-                        void* dv, const void* P, int ldP, void* scratch, long long scratch_bytes, const void* O, hipStream_t s);
+                        void* dv, const void* P, int ldP, void* scratch, long long scratch_bytes, const void* O, hipStream_t s,
+                        const int* cu);
 int attention_fwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, void* o, void* P, void* Pd, int ldP,
-                        hipStream_t s);
+                        hipStream_t s, const int* cu);
+// packed-row forms of the row-wise kernels (norm.hip, elem.hip): nrows / row_of / inv / packed_of NULL = every row, as the C ABI
+// entries.  Kernels that SUM over rows (LayerNorm backward, column sums, the transposes a weight gradient reads) take inv and walk
+// the padded rows, so that their sums have the padded tower's terms in the padded tower's order: the results are bitwise its results
+int ln_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, long long M, int H,
+           float eps, hipStream_t s, const int* nrows);
+int ln_bwd(int dtype, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
+           float* dbeta, float* ws, long long ws_bytes, long long M, int H, hipStream_t s, const int* inv);
+int ln_bwd_pre(int dtype, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx,
+               float* dgamma, float* dbeta, void* dx_dropped, float* dbias, float p, unsigned long long seed, float* ws,
+               long long ws_bytes, long long M, int H, hipStream_t s, const int* inv);
+int transpose_bf16_multi_rows(int count, const void* const* src, void* const* dst, const int32_t* R, const int32_t* Cc,
+                              const int64_t* ld_src, const int64_t* ld_dst, const int* inv, const unsigned char* tok, hipStream_t stream);
+int colsum_rows(int dtype, const void* x, long long M, int N, int ld, float* out, void* ws, long long ws_bytes, int accumulate,
+                const int* inv, hipStream_t s);
+int dropout_rows(int dtype, const void* x, void* out, long long M, int H, float p, unsigned long long seed, const int* nrows,
+                 const int* row_of, hipStream_t s);
+long long bert_row_map_bytes(int B, int L);
+int bert_row_map(const int64_t* mask, int B, int L, int* map, hipStream_t s);
+int bert_unpack_rows(const void* y, void* out, long long rows, long long row_bytes, const int* packed_of, hipStream_t s);
+int bert_pack_rows(const void* dy, void* dst, long long rows, long long row_bytes, const int* nrows, const int* row_of,
+                   hipStream_t s);
+int bert_embed_fwd_rows(int dtype, const int64_t* ids, const float* word, const float* pos, const float* type0, const float* gamma,
+                        const float* beta, void* sum_out, void* y, float* mean, float* rstd, long long tokens, int L, int H, int V,
+                        float eps, float dropout_p, unsigned long long seed, const int* nrows, const int* row_of, hipStream_t stream);
+int bert_embed_bwd_rows(int dtype, const int64_t* ids, const void* dsum, float* dword, float* dpos, int B, int L, int H, int V,
+                        int pad_id, const int* nrows, const int* row_of, const int* packed_of, hipStream_t s);
 
 static inline long long align_up(long long v, long long a) { return (v + a - 1) / a * a; }
 static inline int esize(int dt) { return dt == HS_BF16 ? 2 : 4; }
@@ -79,8 +107,13 @@ struct Run {
     GemmGroup* tower_grp = nullptr;
     // ... and the dY^T transposes those GEMMs read: collected here and made by ONE launch in front of the grouped grid (the
     // row-major gradients stay allocated until then) instead of one launch each where the gradient appears
-    struct PendTr { const void* src; void* dst; int R, C; long long ld; };
+    struct PendTr { const void* src; void* dst; int R, C; long long ld; bool tok; };
     std::vector<PendTr> pend_tr;
+    // BERT tower on packed rows (hs_bert_desc.pack_rows): the device-side row map.  pk_T -> T, the number of rows that exist (the
+    // first T rows of every [B*L][..] buffer); pk_cu [B + 1] first packed row of each sequence; pk_row [B*L] padded row of a packed
+    // row; pk_inv [B*L] packed row of a padded row or -1.  All NULL: every row (every other composite, and the padded tower).
+    // The host never reads them; M, the grids and the arenas stay those of B*L rows.
+    const int *pk_T = nullptr, *pk_cu = nullptr, *pk_row = nullptr, *pk_inv = nullptr;
 };
 
 // one non-blocking side stream and a ring of events per device (events are re-recordable; every composite joins
@@ -293,9 +326,9 @@ static int attention_fwd_run(Run& r, const hs_attn_desc& d, const void* q, const
     if (!r.plan && (knock() & 256)) return HS_OK;
     if (!r.plan && !r.saved.overflow && !r.ws.overflow) {
         // BERT shape (bf16, head dim 64, <= 128 tokens): one fused kernel, scores stay in registers (csrc/attn_fused.hip)
-        const int fused = attention_fwd_fused(d, q, k, v, o, l.P, l.Pd, l.ldP, r.s);
-        if (fused < 0) {
-            set_error("attention_fwd: fused kernel launch failed");
+        const int fused = attention_fwd_fused(d, q, k, v, o, l.P, l.Pd, l.ldP, r.s, r.pk_cu);
+        if (fused < 0 || (fused != 1 && r.pk_cu)) {
+            set_error(r.pk_cu ? "attention_fwd: no packed-row kernel for this shape" : "attention_fwd: fused kernel launch failed");
             return HS_ERR_HIP;
         }
         if (fused == 1) {
@@ -350,9 +383,9 @@ static int attention_bwd_run(Run& r, const hs_attn_desc& d, const void* q, const
     if (!r.plan && !r.saved.overflow && !r.ws.overflow) {
         // BERT shape: one fused kernel (csrc/attn_fused.hip) instead of four batched GEMMs and the softmax backward; beyond
         // 128 keys it keeps its f32 dQ slab in the dP buffer the unfused path would use
-        const int fused = attention_bwd_fused(d, q, k, v, dO, dq, dk, dv, l.P, l.ldP, l.S, (long long)BH * d.Lq * d.Lk * 4, o, r.s);
-        if (fused < 0) {
-            set_error("attention_bwd: fused kernel launch failed");
+        const int fused = attention_bwd_fused(d, q, k, v, dO, dq, dk, dv, l.P, l.ldP, l.S, (long long)BH * d.Lq * d.Lk * 4, o, r.s, r.pk_cu);
+        if (fused < 0 || (fused != 1 && r.pk_cu)) {
+            set_error(r.pk_cu ? "attention_bwd: no packed-row kernel for this shape" : "attention_bwd: fused kernel launch failed");
             return HS_ERR_HIP;
         }
         if (fused == 1) {
@@ -442,6 +475,8 @@ static int linear_fwd_run(Run& r, const void* x, long long M, int ldx, const hs_
     p.D_preact = preact;
     p.residual = residual; p.ldr = ldr;
     p.dropout_p = drop_p; p.dropout_seed = seed;
+    p.m_rows = r.pk_T;                                  // packed rows: tiles behind the last token do nothing
+    p.drop_rows = drop_p > 0.f ? r.pk_row : nullptr;    // ... and a row draws what its padded position draws
     CALL(r, gemm_impl(&p, r.s));
     return HS_OK;
 }
@@ -486,7 +521,8 @@ static int linear_wgrad_run(Run& r, const void* x, long long M, int ldx, const h
         void* dst[2] = {tA, tB};
         const int32_t R[2] = {(int32_t)M, (int32_t)M}, Cc[2] = {lin.out_f, lin.in_f};
         const int64_t lds[2] = {ldy, ldx}, ldd[2] = {M, M};
-        CALLK(r, 4, hs_transpose_bf16_multi(2, src, dst, R, Cc, lds, ldd, r.s));
+        const unsigned char tok[2] = {1, 1};          // packed rows: both operands are token rows, gathered to padded columns
+        CALLK(r, 4, transpose_bf16_multi_rows(2, src, dst, R, Cc, lds, ldd, r.pk_inv, tok, r.s));
         GemmGroup* og = r.plan ? nullptr : open_wgrad_group(r.s);
         const bool keep_flag = r.group_nt;
         GemmGroup* keep_grp = r.grp_nt;
@@ -502,7 +538,7 @@ static int linear_wgrad_run(Run& r, const void* x, long long M, int ldx, const h
         if (lin.db && !fused_b) {
             const long long wsb = hs_colsum_ws_bytes(M, lin.out_f);
             void* w = r.ws.alloc(wsb);
-            CALL(r, hs_colsum(r.dt, dy, M, lin.out_f, ldy, lin.db, w, wsb, 0, r.s));
+            CALL(r, colsum_rows(r.dt, dy, M, lin.out_f, ldy, lin.db, w, wsb, 0, r.pk_inv, r.s));
         }
         // the transposed operands stay allocated while a caller-scoped group may still read them (the plan pass cannot know:
         // it always keeps them, so a plan is never smaller than the run)
@@ -510,6 +546,7 @@ static int linear_wgrad_run(Run& r, const void* x, long long M, int ldx, const h
         return HS_OK;
     }
     if (lin.dw) {
+        HS_REQUIRE(!r.pk_T, "linear_wgrad: packed rows need the transposed-operand weight gradients (HAMSPINE_WGRAD_NT)");
         hs_gemm_params p = gemm_defaults(r.dt);
         p.a_kind = HS_A_RC; p.b_kind = HS_B_RC;
         p.M = lin.out_f; p.N = lin.in_f; p.K = (int)M;
@@ -528,7 +565,7 @@ static int linear_wgrad_run(Run& r, const void* x, long long M, int ldx, const h
         const long long mk = r.ws.mark();
         const long long wsb = hs_colsum_ws_bytes(M, lin.out_f);
         void* w = r.ws.alloc(wsb);
-        CALL(r, hs_colsum(r.dt, dy, M, lin.out_f, ldy, lin.db, w, wsb, 0, r.s));
+        CALL(r, colsum_rows(r.dt, dy, M, lin.out_f, ldy, lin.db, w, wsb, 0, r.pk_inv, r.s));
         if (r.plan ? !overlap_enabled() : !r.side) r.ws.release(mk);
     }
     return HS_OK;
@@ -564,9 +601,21 @@ static bool deferred_transposes_enabled() {     // HAMSPINE_DEFER_TRANSPOSES=0: 
     static const bool on = [] { const char* e = getenv("HAMSPINE_DEFER_TRANSPOSES"); return !(e && e[0] == '0'); }();
     return on;
 }
-static int transpose_run(Run& r, const void* src, void* dst, long long R, int Cc, int ld_src, bool for_grouped_wgrad = false) {
+// tokens: the rows of src are tokens (packed rows: gathered to their padded columns, zeros at masked positions)
+static int transpose_run(Run& r, const void* src, void* dst, long long R, int Cc, int ld_src, bool for_grouped_wgrad = false,
+                         bool tokens = false) {
+    const bool tok = tokens && r.pk_T;
     if (for_grouped_wgrad && r.tower_grp && r.group_nt && !r.plan && deferred_transposes_enabled()) {       // its reader is the tower's grouped grid: see pend_tr
-        r.pend_tr.push_back(Run::PendTr{src, dst, (int)R, Cc, ld_src});
+        r.pend_tr.push_back(Run::PendTr{src, dst, (int)R, Cc, ld_src, tok});
+        return HS_OK;
+    }
+    if (tok) {
+        const void* s1[1] = {src};
+        void* d1[1] = {dst};
+        const int32_t R1[1] = {(int32_t)R}, C1[1] = {Cc};
+        const int64_t ls[1] = {ld_src}, ldst[1] = {R};
+        const unsigned char t1[1] = {1};
+        CALLK(r, 4, transpose_bf16_multi_rows(1, s1, d1, R1, C1, ls, ldst, r.pk_inv, t1, r.s));
         return HS_OK;
     }
     CALLK(r, 4, hs_transpose_bf16(src, dst, (int)R, Cc, ld_src, R, r.s));
@@ -579,12 +628,14 @@ static int pending_transposes_flush(Run& r) {
     std::vector<void*> dst(n);
     std::vector<int32_t> R(n), Cc(n);
     std::vector<int64_t> lds(n), ldd(n);
+    std::vector<unsigned char> tok(n);
     for (int i = 0; i < n; ++i) {
         src[i] = r.pend_tr[i].src; dst[i] = r.pend_tr[i].dst; R[i] = r.pend_tr[i].R; Cc[i] = r.pend_tr[i].C;
         lds[i] = r.pend_tr[i].ld; ldd[i] = r.pend_tr[i].R;
+        tok[i] = r.pend_tr[i].tok ? 1 : 0;
     }
     r.pend_tr.clear();
-    CALLK(r, 4, hs_transpose_bf16_multi(n, src.data(), dst.data(), R.data(), Cc.data(), lds.data(), ldd.data(), r.s));
+    CALLK(r, 4, transpose_bf16_multi_rows(n, src.data(), dst.data(), R.data(), Cc.data(), lds.data(), ldd.data(), r.pk_inv, tok.data(), r.s));
     return HS_OK;
 }
 // seg: 0 = plain; 3 = fused Q/K/V (lin = the q layer; D_seg / rowsum_seg = k, v)
@@ -647,6 +698,7 @@ static int linear_dgrad_run(Run& r, const hs_linear& lin, const void* w_c, const
     p.D = dx; p.ldd = lddx; p.out_dtype = dx_dtype;
     p.mul_mode = mul_mode; p.mul_src = mul_src; p.ldm = ldm;
     p.residual = residual; p.ldr = lddx;
+    p.m_rows = r.pk_T;
     CALLK(r, 1024, gemm_impl(&p, r.s));
     if (mk >= 0 && (r.plan ? !overlap_enabled() : !r.side)) r.ws.release(mk);
     return HS_OK;
@@ -1395,12 +1447,12 @@ static int bert_layer_fwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
     // 3. attention output: h1 = dropout(ctx Wo^T + b) + x ; x1 = LN(h1)
     HS_PROPAGATE(linear_fwd_run(r, L.ctx, M, Hd, d.ao, L.wao, L.h1, Hd, r.dt, HS_ACT_NONE, nullptr, x, Hd, d.hidden_dropout,
                                 d.seed * 8 + 2));
-    CALL(r, hs_layernorm_fwd(r.dt, L.h1, d.ln1.gamma, d.ln1.beta, L.x1, L.mean1, L.rstd1, M, Hd, d.ln_eps, r.s));
+    CALL(r, ln_fwd(r.dt, L.h1, d.ln1.gamma, d.ln1.beta, L.x1, L.mean1, L.rstd1, M, Hd, d.ln_eps, r.s, r.pk_T));
     // 4. FFN
     HS_PROPAGATE(linear_fwd_run(r, L.x1, M, Hd, d.inter_l, L.wi, L.g, I, r.dt, HS_ACT_GELU, L.u, nullptr, 0, 0.f, 0));
     HS_PROPAGATE(linear_fwd_run(r, L.g, M, I, d.out_l, L.wo, L.h2, Hd, r.dt, HS_ACT_NONE, nullptr, L.x1, Hd,
                                 d.hidden_dropout, d.seed * 8 + 3));
-    CALL(r, hs_layernorm_fwd(r.dt, L.h2, d.ln2.gamma, d.ln2.beta, y, L.mean2, L.rstd2, M, Hd, d.ln_eps, r.s));
+    CALL(r, ln_fwd(r.dt, L.h2, d.ln2.gamma, d.ln2.beta, y, L.mean2, L.rstd2, M, Hd, d.ln_eps, r.s, r.pk_T));
     RUN_CHECK_ARENAS(r, "bert_layer_fwd");
     return HS_OK;
 }
@@ -1434,18 +1486,20 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
     const void* g2 = d.hidden_dropout > 0.f ? dd2 : dh2;
     hs_linear out_l_w = d.out_l;
     if (fuse_ln) {
-        CALL(r, hs_layernorm_bwd_pre(r.dt, dy, L.h2, d.ln2.gamma, L.mean2, L.rstd2, dh2, d.ln2.dgamma ? d.ln2.dgamma : scratch,
-                                     d.ln2.dbeta ? d.ln2.dbeta : (scratch ? scratch + Hd : nullptr),
-                                     d.hidden_dropout > 0.f ? dd2 : nullptr, d.out_l.db, d.hidden_dropout, d.seed * 8 + 3,
-                                     ln_ws, ln_ws_bytes, M, Hd, r.s));
+        CALL(r, ln_bwd_pre(r.dt, dy, L.h2, d.ln2.gamma, L.mean2, L.rstd2, dh2, d.ln2.dgamma ? d.ln2.dgamma : scratch,
+                           d.ln2.dbeta ? d.ln2.dbeta : (scratch ? scratch + Hd : nullptr),
+                           d.hidden_dropout > 0.f ? dd2 : nullptr, d.out_l.db, d.hidden_dropout, d.seed * 8 + 3,
+                           ln_ws, ln_ws_bytes, M, Hd, r.s, r.pk_inv));
         out_l_w.db = nullptr;                  // bias gradient already produced above
     } else {
-        CALLK(r, 128, hs_layernorm_bwd(r.dt, dy, L.h2, d.ln2.gamma, L.mean2, L.rstd2, dh2, d.ln2.dgamma ? d.ln2.dgamma : scratch,
-                                 d.ln2.dbeta ? d.ln2.dbeta : (scratch ? scratch + Hd : nullptr), ln_ws, ln_ws_bytes, M, Hd, r.s));
-        if (d.hidden_dropout > 0.f) CALL(r, hs_dropout(r.dt, dh2, dd2, M * Hd, d.hidden_dropout, d.seed * 8 + 3, r.s));
+        CALLK(r, 128, ln_bwd(r.dt, dy, L.h2, d.ln2.gamma, L.mean2, L.rstd2, dh2, d.ln2.dgamma ? d.ln2.dgamma : scratch,
+                             d.ln2.dbeta ? d.ln2.dbeta : (scratch ? scratch + Hd : nullptr), ln_ws, ln_ws_bytes, M, Hd, r.s, r.pk_inv));
+        if (d.hidden_dropout > 0.f && r.pk_T) CALL(r, dropout_rows(r.dt, dh2, dd2, M, Hd, d.hidden_dropout, d.seed * 8 + 3, r.pk_T, r.pk_row, r.s));
+        else if (d.hidden_dropout > 0.f) CALL(r, hs_dropout(r.dt, dh2, dd2, M * Hd, d.hidden_dropout, d.seed * 8 + 3, r.s));
     }
     // bf16: weight gradients from transposed operands (see linear_wgrad_nt_run); tbuf holds the two transposes of one layer
     const bool nt = r.dt == HS_BF16 && wgrad_nt_enabled() && M % 8 == 0 && Hd % 8 == 0 && I % 8 == 0;
+    HS_REQUIRE(!r.pk_T || nt, "bert_layer_bwd: packed rows need the transposed-operand weight gradients (bf16, HAMSPINE_WGRAD_NT on)");
     // grouped: the four GEMMs run together at the end of the layer, so each keeps its own dY^T
     // (only when the four outputs give the chip enough 256x128 tiles: BERT-base 216; a narrow model keeps separate launches)
     const long long big_tiles = (long long)ceil_div(3 * Hd, 256) * ceil_div(Hd, 128) + (long long)ceil_div(Hd, 256) * ceil_div(Hd, 128) +
@@ -1483,7 +1537,7 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
             r.group_nt = keep;
             return st;
         }
-        HS_PROPAGATE(transpose_run(r, dy_rm, tAk, M, lin.out_f, ldy, true));
+        HS_PROPAGATE(transpose_run(r, dy_rm, tAk, M, lin.out_f, ldy, true, true));
         const bool fused_b = lin.db && (r.group_nt || hs_gemm_suggest_split(lin.out_f, in_f, (int)M, r.dt) <= 1) && fused_bias_grad_enabled();
         HS_PROPAGATE(linear_wgrad_nt_run(r, xT, tAk, M, in_f, lin.out_f, lin.dw, lin.db, 0, nullptr, nullptr));
         if (lin.db && !fused_b) HS_PROPAGATE(bias_by_colsum(lin, dy_rm, ldy));
@@ -1499,23 +1553,24 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
         void* dst[7];
         int32_t R[7], Cc[7];
         int64_t lds[7], ldd[7];
+        unsigned char tok[7];
         int n = 0;
-        auto add = [&](const void* s_, void* d_, long long rows, int cols) {
-            src[n] = s_; dst[n] = d_; R[n] = (int32_t)rows; Cc[n] = cols; lds[n] = cols; ldd[n] = rows;
+        auto add = [&](const void* s_, void* d_, long long rows, int cols, bool tokens = false) {
+            src[n] = s_; dst[n] = d_; R[n] = (int32_t)rows; Cc[n] = cols; lds[n] = cols; ldd[n] = rows; tok[n] = tokens ? 1 : 0;
             ++n;
         };
         if (nt) {
-            add(L.g, tX_g, M, I);
-            add(L.x1, tX_x1, M, Hd);
-            add(L.ctx, tX_ctx, M, Hd);
-            add(x, tX_x, M, Hd);
+            add(L.g, tX_g, M, I, true);
+            add(L.x1, tX_x1, M, Hd, true);
+            add(L.ctx, tX_ctx, M, Hd, true);
+            add(x, tX_x, M, Hd, true);
         }
         if (dnt) {
             add(L.wo, wo_t, Hd, I);              // W [out = Hd][in = I] -> [I][Hd]
             add(L.wi, wi_t, I, Hd);
             add(L.wqkv, wqkv_t, 3 * Hd, Hd);
         }
-        if (n > 0) CALLK(r, 4, hs_transpose_bf16_multi(n, src, dst, R, Cc, lds, ldd, r.s));
+        if (n > 0) CALLK(r, 4, transpose_bf16_multi_rows(n, src, dst, R, Cc, lds, ldd, r.pk_inv, tok, r.s));
     }
     HS_PROPAGATE(on_side(r, [&]() { return wgrad(L.g, tX_g, I, out_l_w, g2, Hd, tA_ffn2); }));
     HS_PROPAGATE(linear_dgrad_run(r, d.out_l, L.wo, g2, M, Hd, du, I, r.dt, HS_MUL_GELU_GRAD, L.u, I, nullptr, wo_t));
@@ -1526,15 +1581,16 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
     const void* g1 = d.hidden_dropout > 0.f ? dd1 : dh1;
     hs_linear ao_w = d.ao;
     if (fuse_ln) {
-        CALL(r, hs_layernorm_bwd_pre(r.dt, dx1, L.h1, d.ln1.gamma, L.mean1, L.rstd1, dh1, d.ln1.dgamma ? d.ln1.dgamma : scratch,
-                                     d.ln1.dbeta ? d.ln1.dbeta : (scratch ? scratch + Hd : nullptr),
-                                     d.hidden_dropout > 0.f ? dd1 : nullptr, d.ao.db, d.hidden_dropout, d.seed * 8 + 2,
-                                     ln_ws, ln_ws_bytes, M, Hd, r.s));
+        CALL(r, ln_bwd_pre(r.dt, dx1, L.h1, d.ln1.gamma, L.mean1, L.rstd1, dh1, d.ln1.dgamma ? d.ln1.dgamma : scratch,
+                           d.ln1.dbeta ? d.ln1.dbeta : (scratch ? scratch + Hd : nullptr),
+                           d.hidden_dropout > 0.f ? dd1 : nullptr, d.ao.db, d.hidden_dropout, d.seed * 8 + 2,
+                           ln_ws, ln_ws_bytes, M, Hd, r.s, r.pk_inv));
         ao_w.db = nullptr;
     } else {
-        CALLK(r, 128, hs_layernorm_bwd(r.dt, dx1, L.h1, d.ln1.gamma, L.mean1, L.rstd1, dh1, d.ln1.dgamma ? d.ln1.dgamma : scratch,
-                                 d.ln1.dbeta ? d.ln1.dbeta : (scratch ? scratch + Hd : nullptr), ln_ws, ln_ws_bytes, M, Hd, r.s));
-        if (d.hidden_dropout > 0.f) CALL(r, hs_dropout(r.dt, dh1, dd1, M * Hd, d.hidden_dropout, d.seed * 8 + 2, r.s));
+        CALLK(r, 128, ln_bwd(r.dt, dx1, L.h1, d.ln1.gamma, L.mean1, L.rstd1, dh1, d.ln1.dgamma ? d.ln1.dgamma : scratch,
+                             d.ln1.dbeta ? d.ln1.dbeta : (scratch ? scratch + Hd : nullptr), ln_ws, ln_ws_bytes, M, Hd, r.s, r.pk_inv));
+        if (d.hidden_dropout > 0.f && r.pk_T) CALL(r, dropout_rows(r.dt, dh1, dd1, M, Hd, d.hidden_dropout, d.seed * 8 + 2, r.pk_T, r.pk_row, r.s));
+        else if (d.hidden_dropout > 0.f) CALL(r, hs_dropout(r.dt, dh1, dd1, M * Hd, d.hidden_dropout, d.seed * 8 + 2, r.s));
     }
     HS_PROPAGATE(on_side(r, [&]() { return wgrad(L.ctx, tX_ctx, Hd, ao_w, g1, Hd, tA_ao); }));
     HS_PROPAGATE(linear_dgrad_run(r, d.ao, L.wao, g1, M, Hd, dctx, Hd, r.dt, HS_MUL_NONE, nullptr, 0, nullptr));
@@ -1548,7 +1604,7 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
         // one GEMM for the three weight gradients: [dWq; dWk; dWv] = dqkv^T x, rows routed to the three tensors
         const bool fused = d.q.dw && d.k.dw && d.v.dw;
         if (fused && nt) {
-            HS_PROPAGATE(transpose_run(r, dqkv, tA_qkv, M, 3 * Hd, 3 * Hd, true));
+            HS_PROPAGATE(transpose_run(r, dqkv, tA_qkv, M, 3 * Hd, 3 * Hd, true, true));
             const bool bias_too = d.q.db && d.k.db && d.v.db && (r.group_nt || hs_gemm_suggest_split(3 * Hd, Hd, (int)M, r.dt) <= 1) &&
                                   fused_bias_grad_enabled();
             float* dws[2] = {d.k.dw, d.v.dw};
@@ -1809,7 +1865,16 @@ struct BertTowerLayout {
     long long ssum_off, stats_off;
     long long y_off[HS_BERT_MAX_LAYERS + 1], lay_off[HS_BERT_MAX_LAYERS + 1];
     long long act_bytes;
+    long long map_off, out_off;      // pack_rows: the row map and the padded last_hidden_state (in front of everything else)
 };
+// the row map inside the saved arena (layout: bert_row_map_kernel in elem.hip)
+static void bert_pack_pointers(Run& r, const hs_bert_desc& d, const BertTowerLayout& lo) {
+    const int* map = (const int*)(r.saved.base + lo.map_off);
+    r.pk_T = map;
+    r.pk_cu = map + 4;
+    r.pk_row = r.pk_cu + (d.B + 1 + 3) / 4 * 4;
+    r.pk_inv = r.pk_row + (long long)d.B * d.L;
+}
 static int bert_check(const hs_bert_desc& d) {
     HS_REQUIRE(d.n_layers >= 0 && d.n_layers <= HS_BERT_MAX_LAYERS, "bert: n_layers %d out of range", d.n_layers);
     HS_REQUIRE(d.B > 0 && d.L > 0 && d.hidden > 0 && d.vocab > 0, "bert: bad dims");
@@ -1817,6 +1882,17 @@ static int bert_check(const hs_bert_desc& d) {
     for (int i = 0; i < d.n_layers; ++i)
         HS_REQUIRE(d.layers[i].dtype == d.dtype && d.layers[i].B == d.B && d.layers[i].L == d.L && d.layers[i].hidden == d.hidden,
                    "bert: layer %d shape mismatch", i);
+    if (d.pack_rows) {          // what the packed-row kernels cover; the caller (hamspine.nn.BertModel) asks only inside it
+        HS_REQUIRE(d.dtype == HS_BF16 && d.L <= 128 && d.hidden % 8 == 0 && ((long long)d.B * d.L) % 8 == 0, "bert: pack_rows needs bf16, L <= 128 and hidden %% 8 == 0");
+        for (int i = 0; i < d.n_layers; ++i) {
+            const hs_bert_layer_desc& l = d.layers[i];
+            HS_REQUIRE(l.heads > 0 && d.hidden == 64 * l.heads && l.inter % 8 == 0, "bert: pack_rows needs head dim 64 (layer %d)", i);
+            // the three weight gradients of the fused QKV projection come from ONE GEMM on transposed operands; with only some
+            // of them wanted the layer falls back to per-matrix paths that have no packed form for short batches
+            const int wanted = (l.q.dw != nullptr) + (l.k.dw != nullptr) + (l.v.dw != nullptr);
+            HS_REQUIRE(wanted == 0 || wanted == 3, "bert: pack_rows needs the q / k / v weight gradients of layer %d all wanted or all frozen", i);
+        }
+    }
     return HS_OK;
 }
 static hs_bert_layer_desc bert_layer_of(const hs_bert_desc& d, int i, const int64_t* mask) {
@@ -1829,6 +1905,22 @@ static int bert_fwd_run(Run& r, const hs_bert_desc& d, const int64_t* ids, const
     const long long M = (long long)d.B * d.L;
     const int es = esize(d.dtype);
     lo.act_bytes = M * d.hidden * es;
+    lo.map_off = lo.out_off = 0;
+    char* out_pad = nullptr;
+    if (d.pack_rows) {
+        // Packed rows: one kernel turns the mask into the row map; every kernel below reads the row count from it.  Nothing
+        // comes back to the host, so every buffer keeps its B*L-row size and the packed rows fill its first T rows.
+        HS_REQUIRE(r.plan || mask, "bert_fwd: pack_rows needs an attention mask");
+        lo.map_off = r.saved.mark();
+        int* map = (int*)r.saved.alloc(bert_row_map_bytes(d.B, d.L));
+        lo.out_off = r.saved.mark();
+        out_pad = (char*)r.saved.alloc(lo.act_bytes);
+        if (!r.plan) {
+            RUN_CHECK_ARENAS(r, "bert_fwd(row map)");
+            HS_PROPAGATE(bert_row_map(mask, d.B, d.L, map, r.s));
+            bert_pack_pointers(r, d, lo);
+        }
+    }
     lo.ssum_off = r.saved.mark();
     void* ssum = r.saved.alloc(lo.act_bytes);
     lo.stats_off = r.saved.mark();
@@ -1836,8 +1928,8 @@ static int bert_fwd_run(Run& r, const hs_bert_desc& d, const int64_t* ids, const
     lo.y_off[0] = r.saved.mark();
     char* x = (char*)r.saved.alloc(lo.act_bytes);
     lo.lay_off[0] = r.saved.mark();
-    CALL(r, hs_bert_embed_fwd(d.dtype, ids, d.word, d.pos, d.type0, d.gamma, d.beta, ssum, x, stats, stats + M, M, d.L, d.hidden,
-                              d.vocab, d.ln_eps, d.embed_dropout, d.seed, r.s));
+    CALL(r, bert_embed_fwd_rows(d.dtype, ids, d.word, d.pos, d.type0, d.gamma, d.beta, ssum, x, stats, stats + M, M, d.L, d.hidden,
+                                d.vocab, d.ln_eps, d.embed_dropout, d.seed, r.pk_T, r.pk_row, r.s));
     for (int i = 0; i < d.n_layers; ++i) {
         lo.y_off[i + 1] = r.saved.mark();
         char* y = (char*)r.saved.alloc(lo.act_bytes);
@@ -1848,16 +1940,26 @@ static int bert_fwd_run(Run& r, const hs_bert_desc& d, const int64_t* ids, const
         r.ws.release(wm);
         x = y;
     }
+    // packed rows -> last_hidden_state in the padded layout, zeros at masked positions
+    if (d.pack_rows) CALL(r, bert_unpack_rows(x, out_pad, M, (long long)d.hidden * es, r.pk_inv, r.s));
     return HS_OK;
 }
 static int bert_bwd_run(Run& r, const hs_bert_desc& d, const int64_t* ids, const int64_t* mask, const void* dy_in,
                         const BertTowerLayout& lo) {
     const long long M = (long long)d.B * d.L;
     const int Hd = d.hidden;
+    // packed rows: the cotangent's valid rows are gathered with the forward's map (what arrives at a masked position is ignored)
+    char* dy_packed = d.pack_rows ? (char*)r.ws.alloc(lo.act_bytes) : nullptr;
     char* gbuf[2] = {(char*)r.ws.alloc(lo.act_bytes), (char*)r.ws.alloc(lo.act_bytes)};
     int cur = 0;
     const void* dy = dy_in;
     char* base = r.saved.base;
+    if (d.pack_rows && !r.plan) {
+        RUN_CHECK_ARENAS(r, "bert_bwd(row map)");
+        bert_pack_pointers(r, d, lo);
+        HS_PROPAGATE(bert_pack_rows(dy_in, dy_packed, M, (long long)Hd * esize(d.dtype), r.pk_T, r.pk_row, r.s));
+        dy = dy_packed;
+    }
     // The K-contiguous weight-gradient GEMMs of `span` consecutive layers run as ONE grouped grid (BERT-base, two layers: 8
     // GEMMs = 216 tiles of 256 x 256, one per CU, K = 4096: the phase-pipelined body's steady state -- alone a layer is 108
     // such tiles, or 216 of 256 x 128 on the generic body at half the rate).  The layers' transposed operands stay allocated
@@ -1902,7 +2004,8 @@ static int bert_bwd_run(Run& r, const hs_bert_desc& d, const int64_t* ids, const
     const void* g = dy;
     if (d.embed_dropout > 0.f) {
         char* gd = gbuf[cur];
-        CALL(r, hs_dropout(d.dtype, dy, gd, M * Hd, d.embed_dropout, d.seed, r.s));
+        if (r.pk_T) CALL(r, dropout_rows(d.dtype, dy, gd, M, Hd, d.embed_dropout, d.seed, r.pk_T, r.pk_row, r.s));
+        else CALL(r, hs_dropout(d.dtype, dy, gd, M * Hd, d.embed_dropout, d.seed, r.s));
         g = gd;
         cur ^= 1;
     }
@@ -1913,17 +2016,17 @@ static int bert_bwd_run(Run& r, const hs_bert_desc& d, const int64_t* ids, const
     void* csws = r.ws.alloc(csb);
     float* scratch = (float*)r.ws.alloc(2ll * Hd * 4);
     const float* stats = base ? (const float*)(base + lo.stats_off) : nullptr;
-    CALLK(r, 128, hs_layernorm_bwd(d.dtype, g, base ? base + lo.ssum_off : nullptr, d.gamma, stats, stats ? stats + M : nullptr, dsum,
-                             d.dgamma ? d.dgamma : scratch, d.dbeta ? d.dbeta : (scratch ? scratch + Hd : nullptr), lnws, lnb, M,
-                             Hd, r.s));
+    CALLK(r, 128, ln_bwd(d.dtype, g, base ? base + lo.ssum_off : nullptr, d.gamma, stats, stats ? stats + M : nullptr, dsum,
+                         d.dgamma ? d.dgamma : scratch, d.dbeta ? d.dbeta : (scratch ? scratch + Hd : nullptr), (float*)lnws, lnb, M,
+                         Hd, r.s, r.pk_inv));
     if (!r.plan) {
         if (d.dword) HS_CHECK_HIP(hipMemsetAsync(d.dword, 0, (size_t)d.vocab * Hd * 4, r.s));
         if (d.dpos) HS_CHECK_HIP(hipMemsetAsync(d.dpos, 0, (size_t)d.max_pos * Hd * 4, r.s));
     }
-    if (d.dword || d.dpos) CALL(r, hs_bert_embed_bwd(d.dtype, ids, dsum, d.dword, d.dpos, d.B, d.L, Hd, d.vocab, d.pad_id, r.s));
+    if (d.dword || d.dpos) CALL(r, bert_embed_bwd_rows(d.dtype, ids, dsum, d.dword, d.dpos, d.B, d.L, Hd, d.vocab, d.pad_id, r.pk_T, r.pk_row, r.pk_inv, r.s));
     if (d.dtype0) {
         if (!r.plan && d.n_types > 1) HS_CHECK_HIP(hipMemsetAsync(d.dtype0 + Hd, 0, (size_t)(d.n_types - 1) * Hd * 4, r.s));
-        CALL(r, hs_colsum(d.dtype, dsum, M, Hd, Hd, d.dtype0, csws, csb, 0, r.s));
+        CALL(r, colsum_rows(d.dtype, dsum, M, Hd, Hd, d.dtype0, csws, csb, 0, r.pk_inv, r.s));
     }
     return milestones_flush(r);
 }
@@ -2317,7 +2420,7 @@ hs_status hs_bert_query(const hs_bert_desc* d, int64_t* saved_bytes, int64_t* ws
     HS_PROPAGATE(bert_bwd_run(b, dd, nullptr, nullptr, nullptr, lo));
     if (saved_bytes) *saved_bytes = r.saved.peak;
     if (ws_bytes) *ws_bytes = std::max(r.ws.peak, b.ws.peak);
-    if (out_offset) *out_offset = lo.y_off[d->n_layers];
+    if (out_offset) *out_offset = d->pack_rows ? lo.out_off : lo.y_off[d->n_layers];
     return HS_OK;
 }
 hs_status hs_bert_fwd(const hs_bert_desc* d, const int64_t* ids, const int64_t* mask, void* saved, int64_t saved_bytes,
@@ -2364,6 +2467,9 @@ hs_status hs_bert_bwd(const hs_bert_desc* d, const int64_t* ids, const int64_t* 
 /* weight-gradient side stream inside the composites: 1 on (default, or HAMSPINE_OVERLAP), 0 off (every kernel of a
    composite on the caller's stream, e.g. to time kernels in isolation). */
 void hs_set_overlap(int32_t on) { hs::g_overlap = on ? 1 : 0; }
+/* 1 when the switches this library latched leave the packed-row BERT tower (hs_bert_desc.pack_rows) its kernels: the
+   transposed-operand weight gradients (HAMSPINE_WGRAD_NT / hs_set_wgrad_nt) and the fused attention (HAMSPINE_FUSED_ATTENTION). */
+int32_t hs_bert_pack_rows_available(void) { return (hs::wgrad_nt_enabled() && hs::fused_attention_enabled()) ? 1 : 0; }
 hs_status hs_grad_milestones(int32_t n, const void* const* grad_ptrs, void* const* events) {
     HS_REQUIRE(n >= 0 && n <= kMaxMilestones, "grad_milestones: %d entries (max %d)", n, kMaxMilestones);
     HS_REQUIRE(n == 0 || (grad_ptrs && events), "grad_milestones: null argument");

@@ -283,6 +283,32 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, T
             [&](long long i, float v) { return v * dropout_scale(seed, i, thresh, inv_keep); });
 }
 
+// dropout of packed rows [M][H] (H a multiple of the 16-byte chunk, bases 16-byte aligned): row r draws what its padded
+// position row_of[r] draws in the padded layout (index row_of[r] * H + h), rows >= *nrows are left alone
+template <typename T>
+__global__ __launch_bounds__(256) void dropout_rows_kernel(const T* __restrict__ x, T* __restrict__ o, long long M, int H,
+                                                           const int* __restrict__ nrows, const int* __restrict__ row_of,
+                                                           unsigned thresh, float inv_keep, unsigned long long seed) {
+    constexpr int V = Chunk<T>::N;
+    const int cpr = H / V;
+    const long long rows = packed_rows(nrows, M), total = rows * cpr;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long r = i / cpr;
+        const int c = (int)(i - r * cpr);
+        const unsigned long long base = (unsigned long long)row_of[r] * H + (unsigned long long)c * V;
+        float f[V];
+        Chunk<T>::unpack(*(const u32x4*)(x + r * H + (long long)c * V), f);
+#pragma unroll
+        for (int h = 0; h < V / 4; ++h) {
+            float sc[4];
+            dropout_scale4(seed, base + 4 * h, thresh, inv_keep, sc);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) f[4 * h + k] *= sc[k];
+        }
+        *(u32x4*)(o + r * H + (long long)c * V) = Chunk<T>::pack(f);
+    }
+}
+
 // relu forward / backward (standalone; the fused forms live in the GEMM and BN epilogues)
 template <typename T>
 __global__ __launch_bounds__(256) void relu_kernel(const T* __restrict__ x, T* __restrict__ o, long long n, int al) {
@@ -317,22 +343,33 @@ __global__ __launch_bounds__(256) void mul_dev_scalar_kernel(const float* __rest
 // column sum: X [M][N] -> out[N] (f32), used for bias gradients.  Deterministic two-stage.
 // ============================================================================================
 template <typename T>
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict__ x, long long M, int N, int ld,
-                                                             float* __restrict__ ws) {
+__global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict__ x, long long M_pad, int N, int ld,
+                                                             float* __restrict__ ws, const int* __restrict__ inv) {
     // thread per column, blockIdx.y strides rows (generic, works for any N / ld)
+    // inv (packed rows): the walk is over PADDED rows, row r read from packed row inv[r] and left out where inv[r] < 0 -- the
+    // padded tower adds an exact zero there, so the sums are its sums, term by term in the same order
+    const long long M = M_pad;
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= N) return;
     float acc = 0.f;
-    for (long long r = blockIdx.y; r < M; r += gridDim.y) acc += to_f32(x[r * ld + c]);
+    for (long long r = blockIdx.y; r < M; r += gridDim.y) {
+        long long sr = r;
+        if (inv) {
+            sr = inv[r];
+            if (sr < 0 || sr >= M) continue;
+        }
+        acc += to_f32(x[sr * ld + c]);
+    }
     ws[(long long)blockIdx.y * N + c] = acc;
 }
 // 16-byte variant (N, ld multiples of the chunk, base aligned): a block covers min(64, N / chunk) chunk columns and
 // 256 / that many rows per pass (narrow matrices -- ConvNeXt's 200704 x 128 -- used to leave 3/4 of a 64-column block idle:
 // 155 us); the row lanes merge through LDS in a fixed order
 template <typename T>
-__global__ __launch_bounds__(256) void colsum_partial_vec_kernel(const T* __restrict__ x, long long M, int N, int ld,
-                                                                 float* __restrict__ ws) {
+__global__ __launch_bounds__(256) void colsum_partial_vec_kernel(const T* __restrict__ x, long long M_pad, int N, int ld,
+                                                                 float* __restrict__ ws, const int* __restrict__ inv) {
     constexpr int E = Chunk<T>::N;
+    const long long M = M_pad;                       // inv: as in colsum_partial_kernel
     __shared__ float sh[256][E];
     const int ncol = min(64, N / E - (int)blockIdx.x * 64);     // chunk columns of this block
     const int rpb = 256 / ncol;                                 // rows per pass
@@ -344,8 +381,13 @@ __global__ __launch_bounds__(256) void colsum_partial_vec_kernel(const T* __rest
     for (int e = 0; e < E; ++e) acc[e] = 0.f;
     if (ty < rpb) {
         for (long long r = (long long)blockIdx.y * rpb + ty; r < M; r += (long long)gridDim.y * rpb) {
+            long long sr = r;
+            if (inv) {
+                sr = inv[r];
+                if (sr < 0 || sr >= M) continue;
+            }
             float f[E];
-            Chunk<T>::unpack(*(const u32x4*)(x + r * ld + (long long)cc * E), f);
+            Chunk<T>::unpack(*(const u32x4*)(x + sr * ld + (long long)cc * E), f);
 #pragma unroll
             for (int e = 0; e < E; ++e) acc[e] += f[e];
         }
@@ -593,14 +635,18 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const long long* __restr
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         T* __restrict__ sum_out, T* __restrict__ y, float* __restrict__ mean_out,
                                                         float* __restrict__ rstd_out, long long tokens, int L, int H, int V,
-                                                        float eps, unsigned thresh, float inv_keep, unsigned long long seed) {
+                                                        float eps, unsigned thresh, float inv_keep, unsigned long long seed,
+                                                        const int* __restrict__ nrows, const int* __restrict__ row_of) {
     const int lane = threadIdx.x & 63;
     const long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= tokens) return;
-    long long id = ids[t];
+    if (t >= packed_rows(nrows, tokens)) return;
+    // packed rows: row t is written from the token at padded position src (its id, its position, its dropout draw)
+    long long src = row_of ? (long long)row_of[t] : t;
+    if (src < 0 || src >= tokens) src = t;
+    long long id = ids[src];
     if (id < 0) id = 0;
     if (id >= V) id = V - 1;
-    const int l = (int)(t % L);
+    const int l = (int)(src % L);
     const int nch = H / 4;
     float v[4][4];
     float s = 0.f;
@@ -645,7 +691,7 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const long long* __restr
                 const int h = c * 4 + e;
                 sum_out[t * H + h] = from_f32<T>(v[i][e]);
                 float o = (v[i][e] - mean) * rstd * gamma[h] + beta[h];
-                if (thresh) o *= dropout_scale(seed, (unsigned long long)t * H + h, thresh, inv_keep);
+                if (thresh) o *= dropout_scale(seed, (unsigned long long)src * H + h, thresh, inv_keep);
                 y[t * H + h] = from_f32<T>(o);
             }
     }
@@ -659,18 +705,27 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const long long* __restr
 __device__ __forceinline__ long long clamp_id(long long id, int V) { return id < 0 ? 0 : (id >= V ? V - 1 : id); }
 template <typename T>
 __global__ __launch_bounds__(256) void embed_word_bwd_kernel(const long long* __restrict__ ids, const T* __restrict__ dsum,
-                                                             float* __restrict__ dword, int tokens, int H, int V,
-                                                             int pad_id) {
+                                                             float* __restrict__ dword, int tokens_pad, int H, int V,
+                                                             int pad_id, const int* __restrict__ nrows,
+                                                             const int* __restrict__ row_of) {
     extern __shared__ __attribute__((aligned(16))) int s_mem[];   // [tokens] match list + [8] wave totals
     int* s_list = s_mem;
-    int* s_wave = s_mem + tokens;
+    int* s_wave = s_mem + tokens_pad;
+    // packed rows: dsum row i belongs to the token at padded position row_of[i]; rows >= *nrows do not exist
+    const int tokens = (int)packed_rows(nrows, tokens_pad);
     const int t = blockIdx.x;
-    const long long id = clamp_id(ids[t], V);
+    if (t >= tokens) return;                                      // block-uniform
+    auto id_at = [&](int i) -> long long {
+        long long srow = row_of ? (long long)row_of[i] : (long long)i;
+        if (srow < 0 || srow >= tokens_pad) srow = i;
+        return clamp_id(ids[srow], V);
+    };
+    const long long id = id_at(t);
     if (id == pad_id) return;                                     // block-uniform
     const int per = (tokens + 255) / 256;
     const int lo = min((int)threadIdx.x * per, tokens), hi = min(lo + per, tokens);
     int c = 0;
-    for (int i = lo; i < hi; ++i) c += clamp_id(ids[i], V) == id ? 1 : 0;
+    for (int i = lo; i < hi; ++i) c += id_at(i) == id ? 1 : 0;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int incl = c;                                                 // inclusive scan inside the wave
     for (int o = 1; o < 64; o <<= 1) {
@@ -683,7 +738,7 @@ __global__ __launch_bounds__(256) void embed_word_bwd_kernel(const long long* __
     for (int w = 0; w < wv; ++w) off += s_wave[w];
     const int n = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
     for (int i = lo; i < hi; ++i)
-        if (clamp_id(ids[i], V) == id) s_list[off++] = i;
+        if (id_at(i) == id) s_list[off++] = i;
     __syncthreads();
     if (s_list[0] != t) return;                                   // a smaller token index owns this id (block-uniform)
     for (int h = threadIdx.x; h < H; h += 256) {
@@ -696,12 +751,15 @@ __global__ __launch_bounds__(256) void embed_word_bwd_kernel(const long long* __
 template <typename T>
 __global__ __launch_bounds__(256) void embed_word_bwd_atomic_kernel(const long long* __restrict__ ids,
                                                                     const T* __restrict__ dsum, float* __restrict__ dword,
-                                                                    long long tokens, int H, int V, int pad_id) {
-    const long long total = tokens * H;
+                                                                    long long tokens_pad, int H, int V, int pad_id,
+                                                                    const int* __restrict__ nrows, const int* __restrict__ row_of) {
+    const long long total = packed_rows(nrows, tokens_pad) * H;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const long long t = i / H;
         const int h = (int)(i % H);
-        const long long id = clamp_id(ids[t], V);
+        long long srow = row_of ? (long long)row_of[t] : t;
+        if (srow < 0 || srow >= tokens_pad) srow = t;
+        const long long id = clamp_id(ids[srow], V);
         if (id == pad_id) continue;
         atomicAdd(dword + id * H + h, to_f32(dsum[i]));
     }
@@ -709,12 +767,98 @@ __global__ __launch_bounds__(256) void embed_word_bwd_atomic_kernel(const long l
 // dpos[l][h] = sum_b dsum[b][l][h]   (rows l >= L are zeroed by the caller)
 template <typename T>
 __global__ __launch_bounds__(256) void embed_pos_bwd_kernel(const T* __restrict__ dsum, float* __restrict__ dpos, int B,
-                                                            int L, int H) {
+                                                            int L, int H, const int* __restrict__ packed_of) {
     const long long total = (long long)L * H;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         float acc = 0.f;
-        for (int b = 0; b < B; ++b) acc += to_f32(dsum[(long long)b * L * H + i]);
+        if (packed_of) {           // packed rows: token (b, l) sits in dsum row packed_of[b * L + l], or nowhere (-1)
+            const int l = (int)(i / H), h = (int)(i - (long long)l * H);
+            for (int b = 0; b < B; ++b) {
+                const int pr = packed_of[(long long)b * L + l];
+                if (pr >= 0 && pr < B * L) acc += to_f32(dsum[(long long)pr * H + h]);
+            }
+        } else {
+            for (int b = 0; b < B; ++b) acc += to_f32(dsum[(long long)b * L * H + i]);
+        }
         dpos[i] = acc;
+    }
+}
+
+// ============================================================================================
+// Packed rows of the BERT tower (hs_bert_desc.pack_rows): the row map, made on the device from attention_mask [B][L].
+//   map[0] = T (valid tokens); cu = map + 4: [B + 1] exclusive prefix sum of the valid counts; row_of = cu + roundup(B + 1, 4):
+//   [B*L] padded row b*L + l of packed row t (row_of[t] = t for t >= T, so any index read from it stays inside the buffers);
+//   packed_of = row_of + B*L: [B*L] packed row of a padded row, -1 where the mask is 0.
+// One workgroup; a wave per sequence, 64 positions per step (ballot + popcount keep the tokens in order).
+// ============================================================================================
+__global__ __launch_bounds__(256) void bert_row_map_kernel(const long long* __restrict__ mask, int B, int L, int* __restrict__ map) {
+    int* cu = map + 4;
+    int* row_of = cu + (B + 1 + 3) / 4 * 4;
+    int* packed_of = row_of + (long long)B * L;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int b = wave; b < B; b += 4) {                       // pass 1: valid tokens per sequence -> cu[b + 1]
+        int n = 0;
+        for (int l0 = 0; l0 < L; l0 += 64) {
+            const int l = l0 + lane;
+            const bool v = l < L && mask[(long long)b * L + l] != 0;
+            n += __popcll(__ballot(v));
+        }
+        if (lane == 0) cu[b + 1] = n;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                   // exclusive prefix sum in place (B is a batch size: a short serial walk)
+        int run = 0;
+        cu[0] = 0;
+        for (int b = 0; b < B; ++b) {
+            run += cu[b + 1];
+            cu[b + 1] = run;
+        }
+        map[0] = run;
+        map[1] = map[2] = map[3] = 0;
+    }
+    __syncthreads();
+    const int T = cu[B];
+    for (int b = wave; b < B; b += 4) {                       // pass 2: the two index arrays
+        int at = cu[b];
+        for (int l0 = 0; l0 < L; l0 += 64) {
+            const int l = l0 + lane;
+            const bool v = l < L && mask[(long long)b * L + l] != 0;
+            const unsigned long long bal = __ballot(v);
+            const int before = __popcll(bal & ((1ull << lane) - 1ull));
+            if (l < L) {
+                if (v) {
+                    row_of[at + before] = b * L + l;
+                    packed_of[(long long)b * L + l] = at + before;
+                } else {
+                    packed_of[(long long)b * L + l] = -1;
+                }
+            }
+            at += __popcll(bal);
+        }
+    }
+    for (int t = T + (int)threadIdx.x; t < B * L; t += 256) row_of[t] = t;
+}
+// last_hidden_state in the padded layout from packed rows, zeros at masked positions: out[row] = packed_of[row] >= 0 ? y[packed_of[row]] : 0
+__global__ __launch_bounds__(256) void bert_unpack_rows_kernel(const u32x4* __restrict__ y, u32x4* __restrict__ out, long long rows, int cpr,
+                                                               const int* __restrict__ packed_of) {
+    const long long total = rows * cpr;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long r = i / cpr;
+        const int pr = packed_of[r];
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (pr >= 0 && pr < rows) v = y[(long long)pr * cpr + (i - r * cpr)];
+        out[i] = v;
+    }
+}
+// the incoming cotangent's valid rows, packed: dst[t] = dy[row_of[t]] for t < T (what sits at masked positions is ignored)
+__global__ __launch_bounds__(256) void bert_pack_rows_kernel(const u32x4* __restrict__ dy, u32x4* __restrict__ dst, long long rows, int cpr,
+                                                             const int* __restrict__ nrows, const int* __restrict__ row_of) {
+    const long long T = packed_rows(nrows, rows), total = T * cpr;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long t = i / cpr;
+        long long srow = row_of[t];
+        if (srow < 0 || srow >= rows) srow = t;
+        dst[i] = dy[srow * cpr + (i - t * cpr)];
     }
 }
 
@@ -728,14 +872,22 @@ __global__ __launch_bounds__(256) void embed_pos_bwd_kernel(const T* __restrict_
 // read phase has rows 8k + q and 8(k + 4) + q in one 32-lane group, which a pitch alone leaves on the same bank (PMC: 40 % of
 // the LDS cycles were conflicts); 16-byte global accesses.
 // ============================================================================================
+// inv (packed rows, else NULL): the source holds PACKED token rows; column r of the result is the token at padded row r, read
+// from source row inv[r], or zeros where inv[r] < 0.  The transposed copy is thus the padded tower's (which holds exact zeros
+// in dY^T at masked positions), so the weight gradient that reads it sums the same terms in the same order.
 __device__ __forceinline__ void transpose_bf16_tile(const unsigned short* __restrict__ src, unsigned short* __restrict__ dst,
                                                     int R, int Cc, long long lds_, long long ldd, int bx, int by,
-                                                    unsigned (*tile)[33]) {
+                                                    unsigned (*tile)[33], const int* __restrict__ inv) {
     const int r0 = by * 64, c0 = bx * 64;
     for (int i = threadIdx.x; i < 512; i += 256) {
         const int r = i >> 3, ch = i & 7;
         u32x4 v = {0u, 0u, 0u, 0u};
-        if (r0 + r < R && c0 + ch * 8 < Cc) v = *(const u32x4*)(src + (long long)(r0 + r) * lds_ + c0 + ch * 8);
+        int sr = r0 + r;
+        if (inv && sr < R) {
+            sr = inv[sr];
+            if (sr >= R) sr = -1;
+        }
+        if (sr >= 0 && sr < R && c0 + ch * 8 < Cc) v = *(const u32x4*)(src + (long long)sr * lds_ + c0 + ch * 8);
 #pragma unroll
         for (int w = 0; w < 4; ++w) tile[r][(ch * 4 + w) ^ ((r >> 5) << 2)] = v[w];
     }
@@ -757,7 +909,7 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const unsigned shor
                                                              unsigned short* __restrict__ dst, int R, int Cc, long long lds_,
                                                              long long ldd) {
     __shared__ unsigned tile[64][33];
-    transpose_bf16_tile(src, dst, R, Cc, lds_, ldd, blockIdx.x, blockIdx.y, tile);
+    transpose_bf16_tile(src, dst, R, Cc, lds_, ldd, blockIdx.x, blockIdx.y, tile, nullptr);
 }
 // several matrices in one grid (a BertLayer's backward transposes four saved activations and three weight copies before it
 // starts: seven 7 us launches become one)
@@ -768,6 +920,8 @@ struct TransposeTable {
     long long ld_src[HS_TRANSPOSE_MAX], ld_dst[HS_TRANSPOSE_MAX];
     int first[HS_TRANSPOSE_MAX + 1];      // first workgroup of entry i; first[count] = grid size
     int count;
+    const int* inv;                       // packed rows: packed row of a padded row (-1: none) for the entries in tok_mask
+    unsigned tok_mask;                    // bit i: the rows of entry i are packed tokens
 };
 __global__ __launch_bounds__(256) void transpose_bf16_multi_kernel(const TransposeTable t) {
     __shared__ unsigned tile[64][33];
@@ -775,7 +929,8 @@ __global__ __launch_bounds__(256) void transpose_bf16_multi_kernel(const Transpo
     for (int i = 1; i < t.count; ++i) e += (int)blockIdx.x >= t.first[i];
     const int local = blockIdx.x - t.first[e];
     const int tx = (t.C[e] + 63) / 64;
-    transpose_bf16_tile(t.src[e], t.dst[e], t.R[e], t.C[e], t.ld_src[e], t.ld_dst[e], local % tx, local / tx, tile);
+    const int* inv = (t.inv && ((t.tok_mask >> e) & 1u)) ? t.inv : nullptr;
+    transpose_bf16_tile(t.src[e], t.dst[e], t.R[e], t.C[e], t.ld_src[e], t.ld_dst[e], local % tx, local / tx, tile, inv);
 }
 
 // ============================================================================================
@@ -989,16 +1144,16 @@ static inline int colsum_gy(long long M, int N) {
 }
 template <typename T>
 static int colsum_t(const void* x, long long M, int N, int ld, float* out, float* ws, long long ws_bytes, int accumulate,
-                    hipStream_t s) {
+                    hipStream_t s, const int* inv = nullptr) {
     constexpr int E = Chunk<T>::N;
     const int gy = colsum_gy(M, N);
     HS_REQUIRE(ws && ws_bytes >= (long long)gy * N * 4, "colsum: workspace too small");
     const bool direct = gy == 1 && !accumulate;        // one row group: its sums go straight to `out`, no second launch
     if (direct) ws = out;
     if (N % E == 0 && ld % E == 0 && ((((uintptr_t)x) & 15) == 0))
-        hipLaunchKernelGGL(colsum_partial_vec_kernel<T>, dim3(ceil_div(N / E, 64), gy), dim3(256), 0, s, (const T*)x, M, N, ld, ws);
+        hipLaunchKernelGGL(colsum_partial_vec_kernel<T>, dim3(ceil_div(N / E, 64), gy), dim3(256), 0, s, (const T*)x, M, N, ld, ws, inv);
     else
-        hipLaunchKernelGGL(colsum_partial_kernel<T>, dim3(ceil_div(N, 256), gy), dim3(256), 0, s, (const T*)x, M, N, ld, ws);
+        hipLaunchKernelGGL(colsum_partial_kernel<T>, dim3(ceil_div(N, 256), gy), dim3(256), 0, s, (const T*)x, M, N, ld, ws, inv);
     HS_LAUNCH_CHECK();
     if (direct) return HS_OK;
     hipLaunchKernelGGL(colsum_final_kernel, dim3(ceil_div(N, 64)), dim3(256), 0, s, ws, gy, N, out, accumulate);
@@ -1052,6 +1207,131 @@ static int softmax_bwd_t(const float* dP, const void* P, void* dS, long long row
     return HS_OK;
 }
 
+// ---- packed-row entry points (C++ only: the BERT tower executor in blocks.hip) -----------------------------------------------
+// tok[k] != 0: the rows of entry k are packed tokens, gathered to their padded positions through inv (see transpose_bf16_tile)
+int transpose_bf16_multi_rows(int count, const void* const* src, void* const* dst, const int32_t* R, const int32_t* Cc,
+                              const int64_t* ld_src, const int64_t* ld_dst, const int* inv, const unsigned char* tok, hipStream_t stream) {
+    HS_REQUIRE(count >= 0 && (count == 0 || (src && dst && R && Cc && ld_src && ld_dst)), "transpose_bf16_multi: bad argument");
+    for (int base = 0; base < count; base += HS_TRANSPOSE_MAX) {
+        TransposeTable t;
+        memset(&t, 0, sizeof(t));
+        t.count = std::min(HS_TRANSPOSE_MAX, count - base);
+        int blocks = 0;
+        for (int i = 0; i < t.count; ++i) {
+            const int k = base + i;
+            HS_REQUIRE(src[k] && dst[k] && R[k] > 0 && Cc[k] > 0 && R[k] % 8 == 0 && Cc[k] % 8 == 0 && ld_src[k] % 8 == 0 &&
+                           ld_dst[k] % 8 == 0 && ld_src[k] >= Cc[k] && ld_dst[k] >= R[k] &&
+                           (((uintptr_t)src[k] | (uintptr_t)dst[k]) & 15) == 0,
+                       "transpose_bf16_multi: entry %d: dims / leading dimensions must be multiples of 8 and bases 16-byte aligned", k);
+            t.src[i] = (const unsigned short*)src[k];
+            t.dst[i] = (unsigned short*)dst[k];
+            t.R[i] = R[k]; t.C[i] = Cc[k];
+            t.ld_src[i] = ld_src[k]; t.ld_dst[i] = ld_dst[k];
+            t.first[i] = blocks;
+            blocks += ceil_div(Cc[k], 64) * ceil_div(R[k], 64);
+            if (inv && tok && tok[k]) t.tok_mask |= 1u << i;
+        }
+        t.first[t.count] = blocks;
+        t.inv = t.tok_mask ? inv : nullptr;
+        hipLaunchKernelGGL(transpose_bf16_multi_kernel, dim3(blocks), dim3(256), 0, stream, t);
+        HS_LAUNCH_CHECK();
+    }
+    return HS_OK;
+}
+int colsum_rows(int dtype, const void* x, long long M, int N, int ld, float* out, void* ws, long long ws_bytes, int accumulate,
+                const int* inv, hipStream_t s) {
+    HS_REQUIRE(x && out && M > 0 && N > 0, "colsum: bad argument");
+    return DISPATCH_T(dtype, colsum_t, x, M, N, ld, out, (float*)ws, ws_bytes, accumulate, s, inv);
+}
+int dropout_rows(int dtype, const void* x, void* out, long long M, int H, float p, unsigned long long seed, const int* nrows,
+                 const int* row_of, hipStream_t s) {
+    HS_REQUIRE(x && out && nrows && row_of && p >= 0.f && p < 1.f, "dropout_rows: bad argument");
+    HS_REQUIRE(H % 8 == 0 && al16(x, out), "dropout_rows: H %% 8 != 0 or unaligned base");
+    const unsigned th = dropout_thresh(p);
+    const float ik = 1.f / (1.f - p);
+    if (dtype == HS_BF16)
+        hipLaunchKernelGGL(dropout_rows_kernel<bf16_t>, dim3(grid_for(M * (H / 8))), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out, M, H,
+                           nrows, row_of, th, ik, seed);
+    else
+        hipLaunchKernelGGL(dropout_rows_kernel<float>, dim3(grid_for(M * (H / 4))), dim3(256), 0, s, (const float*)x, (float*)out, M, H,
+                           nrows, row_of, th, ik, seed);
+    HS_LAUNCH_CHECK();
+    return HS_OK;
+}
+long long bert_row_map_bytes(int B, int L) { return (4ll + (B + 1 + 3) / 4 * 4 + 2ll * B * L) * 4; }
+int bert_row_map(const int64_t* mask, int B, int L, int* map, hipStream_t s) {
+    HS_REQUIRE(mask && map && B > 0 && L > 0, "bert_row_map: bad argument");
+    hipLaunchKernelGGL(bert_row_map_kernel, dim3(1), dim3(256), 0, s, (const long long*)mask, B, L, map);
+    HS_LAUNCH_CHECK();
+    return HS_OK;
+}
+// rows of `row_bytes` bytes (a multiple of 16, bases 16-byte aligned)
+int bert_unpack_rows(const void* y, void* out, long long rows, long long row_bytes, const int* packed_of, hipStream_t s) {
+    HS_REQUIRE(y && out && packed_of && row_bytes % 16 == 0 && al16(y, out), "bert_unpack_rows: bad argument");
+    const int cpr = (int)(row_bytes / 16);
+    hipLaunchKernelGGL(bert_unpack_rows_kernel, dim3(grid_for(rows * cpr)), dim3(256), 0, s, (const u32x4*)y, (u32x4*)out, rows, cpr, packed_of);
+    HS_LAUNCH_CHECK();
+    return HS_OK;
+}
+int bert_pack_rows(const void* dy, void* dst, long long rows, long long row_bytes, const int* nrows, const int* row_of,
+                   hipStream_t s) {
+    HS_REQUIRE(dy && dst && nrows && row_of && row_bytes % 16 == 0 && al16(dy, dst), "bert_pack_rows: bad argument");
+    const int cpr = (int)(row_bytes / 16);
+    hipLaunchKernelGGL(bert_pack_rows_kernel, dim3(grid_for(rows * cpr)), dim3(256), 0, s, (const u32x4*)dy, (u32x4*)dst, rows, cpr, nrows,
+                       row_of);
+    HS_LAUNCH_CHECK();
+    return HS_OK;
+}
+int bert_embed_fwd_rows(int dtype, const int64_t* ids, const float* word, const float* pos, const float* type0, const float* gamma,
+                        const float* beta, void* sum_out, void* y, float* mean, float* rstd, long long tokens, int L, int H, int V,
+                        float eps, float dropout_p, unsigned long long seed, const int* nrows, const int* row_of, hipStream_t stream) {
+    HS_REQUIRE(ids && word && pos && type0 && gamma && beta && sum_out && y && mean && rstd, "bert_embed: null argument");
+    HS_REQUIRE(H % 4 == 0 && H <= 1024, "bert_embed: H=%d unsupported", H);
+    const unsigned th = dropout_p > 0.f ? dropout_thresh(dropout_p) : 0u;
+    const float ik = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
+    const dim3 g(ceil_div(tokens, 4)), b(256);
+    if (dtype == HS_BF16)
+        hipLaunchKernelGGL(embed_fwd_kernel<bf16_t>, g, b, 0, stream, (const long long*)ids, word, pos, type0,
+                           gamma, beta, (bf16_t*)sum_out, (bf16_t*)y, mean, rstd, tokens, L, H, V, eps, th, ik, seed, nrows, row_of);
+    else
+        hipLaunchKernelGGL(embed_fwd_kernel<float>, g, b, 0, stream, (const long long*)ids, word, pos, type0,
+                           gamma, beta, (float*)sum_out, (float*)y, mean, rstd, tokens, L, H, V, eps, th, ik, seed, nrows, row_of);
+    HS_LAUNCH_CHECK();
+    return HS_OK;
+}
+// nrows / row_of / packed_of: all three or none (packed rows: dsum row t belongs to padded position row_of[t])
+int bert_embed_bwd_rows(int dtype, const int64_t* ids, const void* dsum, float* dword, float* dpos, int B, int L, int H, int V,
+                        int pad_id, const int* nrows, const int* row_of, const int* packed_of, hipStream_t s) {
+    HS_REQUIRE(ids && dsum, "bert_embed_bwd: null argument");
+    const long long tokens = (long long)B * L;
+    if (dword) {   // caller zero-fills dword first
+        const bool det = tokens <= 15360;                 // match list (4 B per token) + wave totals within 64 KiB of LDS
+        const size_t lds = det ? (size_t)(tokens + 8) * sizeof(int) : 0;
+        if (det && dtype == HS_BF16)
+            hipLaunchKernelGGL(embed_word_bwd_kernel<bf16_t>, dim3((unsigned)tokens), dim3(256), lds, s, (const long long*)ids,
+                               (const bf16_t*)dsum, dword, (int)tokens, H, V, pad_id, nrows, row_of);
+        else if (det)
+            hipLaunchKernelGGL(embed_word_bwd_kernel<float>, dim3((unsigned)tokens), dim3(256), lds, s, (const long long*)ids,
+                               (const float*)dsum, dword, (int)tokens, H, V, pad_id, nrows, row_of);
+        else if (dtype == HS_BF16)
+            hipLaunchKernelGGL(embed_word_bwd_atomic_kernel<bf16_t>, dim3(grid_for(tokens * H)), dim3(256), 0, s,
+                               (const long long*)ids, (const bf16_t*)dsum, dword, tokens, H, V, pad_id, nrows, row_of);
+        else
+            hipLaunchKernelGGL(embed_word_bwd_atomic_kernel<float>, dim3(grid_for(tokens * H)), dim3(256), 0, s,
+                               (const long long*)ids, (const float*)dsum, dword, tokens, H, V, pad_id, nrows, row_of);
+        HS_LAUNCH_CHECK();
+    }
+    if (dpos) {
+        if (dtype == HS_BF16)
+            hipLaunchKernelGGL(embed_pos_bwd_kernel<bf16_t>, dim3(grid_for((long long)L * H)), dim3(256), 0, s,
+                               (const bf16_t*)dsum, dpos, B, L, H, packed_of);
+        else
+            hipLaunchKernelGGL(embed_pos_bwd_kernel<float>, dim3(grid_for((long long)L * H)), dim3(256), 0, s,
+                               (const float*)dsum, dpos, B, L, H, packed_of);
+        HS_LAUNCH_CHECK();
+    }
+    return HS_OK;
+}
 }  // namespace hs
 
 using namespace hs;
@@ -1222,52 +1502,12 @@ hs_status hs_bert_embed_fwd(int32_t dtype, const int64_t* ids, const float* word
                             const float* gamma, const float* beta, void* sum_out, void* y, float* mean, float* rstd,
                             int64_t tokens, int32_t L, int32_t H, int32_t V, float eps, float dropout_p, uint64_t seed,
                             void* stream) {
-    HS_REQUIRE(ids && word && pos && type0 && gamma && beta && sum_out && y && mean && rstd, "bert_embed: null argument");
-    HS_REQUIRE(H % 4 == 0 && H <= 1024, "bert_embed: H=%d unsupported", H);
-    const unsigned th = dropout_p > 0.f ? dropout_thresh(dropout_p) : 0u;
-    const float ik = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
-    const dim3 g(ceil_div(tokens, 4)), b(256);
-    if (dtype == HS_BF16)
-        hipLaunchKernelGGL(embed_fwd_kernel<bf16_t>, g, b, 0, (hipStream_t)stream, (const long long*)ids, word, pos, type0,
-                           gamma, beta, (bf16_t*)sum_out, (bf16_t*)y, mean, rstd, tokens, L, H, V, eps, th, ik, seed);
-    else
-        hipLaunchKernelGGL(embed_fwd_kernel<float>, g, b, 0, (hipStream_t)stream, (const long long*)ids, word, pos, type0,
-                           gamma, beta, (float*)sum_out, (float*)y, mean, rstd, tokens, L, H, V, eps, th, ik, seed);
-    HS_LAUNCH_CHECK();
-    return HS_OK;
+    return hs::bert_embed_fwd_rows(dtype, ids, word, pos, type0, gamma, beta, sum_out, y, mean, rstd, tokens, L, H, V, eps, dropout_p,
+                                   seed, nullptr, nullptr, (hipStream_t)stream);
 }
 hs_status hs_bert_embed_bwd(int32_t dtype, const int64_t* ids, const void* dsum, float* dword, float* dpos, int32_t B,
                             int32_t L, int32_t H, int32_t V, int32_t pad_id, void* stream) {
-    HS_REQUIRE(ids && dsum, "bert_embed_bwd: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    const long long tokens = (long long)B * L;
-    if (dword) {   // caller zero-fills dword first
-        const bool det = tokens <= 15360;                 // match list (4 B per token) + wave totals within 64 KiB of LDS
-        const size_t lds = det ? (size_t)(tokens + 8) * sizeof(int) : 0;
-        if (det && dtype == HS_BF16)
-            hipLaunchKernelGGL(embed_word_bwd_kernel<bf16_t>, dim3((unsigned)tokens), dim3(256), lds, s, (const long long*)ids,
-                               (const bf16_t*)dsum, dword, (int)tokens, H, V, pad_id);
-        else if (det)
-            hipLaunchKernelGGL(embed_word_bwd_kernel<float>, dim3((unsigned)tokens), dim3(256), lds, s, (const long long*)ids,
-                               (const float*)dsum, dword, (int)tokens, H, V, pad_id);
-        else if (dtype == HS_BF16)
-            hipLaunchKernelGGL(embed_word_bwd_atomic_kernel<bf16_t>, dim3(grid_for(tokens * H)), dim3(256), 0, s,
-                               (const long long*)ids, (const bf16_t*)dsum, dword, tokens, H, V, pad_id);
-        else
-            hipLaunchKernelGGL(embed_word_bwd_atomic_kernel<float>, dim3(grid_for(tokens * H)), dim3(256), 0, s,
-                               (const long long*)ids, (const float*)dsum, dword, tokens, H, V, pad_id);
-        HS_LAUNCH_CHECK();
-    }
-    if (dpos) {
-        if (dtype == HS_BF16)
-            hipLaunchKernelGGL(embed_pos_bwd_kernel<bf16_t>, dim3(grid_for((long long)L * H)), dim3(256), 0, s,
-                               (const bf16_t*)dsum, dpos, B, L, H);
-        else
-            hipLaunchKernelGGL(embed_pos_bwd_kernel<float>, dim3(grid_for((long long)L * H)), dim3(256), 0, s,
-                               (const float*)dsum, dpos, B, L, H);
-        HS_LAUNCH_CHECK();
-    }
-    return HS_OK;
+    return hs::bert_embed_bwd_rows(dtype, ids, dsum, dword, dpos, B, L, H, V, pad_id, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 hs_status hs_transpose_bf16(const void* src, void* dst, int32_t R, int32_t Cc, int64_t ld_src, int64_t ld_dst, void* stream) {
     HS_REQUIRE(src && dst && R > 0 && Cc > 0, "transpose_bf16: bad argument");
@@ -1281,30 +1521,7 @@ hs_status hs_transpose_bf16(const void* src, void* dst, int32_t R, int32_t Cc, i
 }
 hs_status hs_transpose_bf16_multi(int32_t count, const void* const* src, void* const* dst, const int32_t* R, const int32_t* Cc,
                                   const int64_t* ld_src, const int64_t* ld_dst, void* stream) {
-    HS_REQUIRE(count >= 0 && (count == 0 || (src && dst && R && Cc && ld_src && ld_dst)), "transpose_bf16_multi: bad argument");
-    for (int base = 0; base < count; base += HS_TRANSPOSE_MAX) {
-        TransposeTable t;
-        memset(&t, 0, sizeof(t));
-        t.count = std::min(HS_TRANSPOSE_MAX, count - base);
-        int blocks = 0;
-        for (int i = 0; i < t.count; ++i) {
-            const int k = base + i;
-            HS_REQUIRE(src[k] && dst[k] && R[k] > 0 && Cc[k] > 0 && R[k] % 8 == 0 && Cc[k] % 8 == 0 && ld_src[k] % 8 == 0 &&
-                           ld_dst[k] % 8 == 0 && ld_src[k] >= Cc[k] && ld_dst[k] >= R[k] &&
-                           (((uintptr_t)src[k] | (uintptr_t)dst[k]) & 15) == 0,
-                       "transpose_bf16_multi: entry %d: dims / leading dimensions must be multiples of 8 and bases 16-byte aligned", k);
-            t.src[i] = (const unsigned short*)src[k];
-            t.dst[i] = (unsigned short*)dst[k];
-            t.R[i] = R[k]; t.C[i] = Cc[k];
-            t.ld_src[i] = ld_src[k]; t.ld_dst[i] = ld_dst[k];
-            t.first[i] = blocks;
-            blocks += ceil_div(Cc[k], 64) * ceil_div(R[k], 64);
-        }
-        t.first[t.count] = blocks;
-        hipLaunchKernelGGL(transpose_bf16_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, t);
-        HS_LAUNCH_CHECK();
-    }
-    return HS_OK;
+    return hs::transpose_bf16_multi_rows(count, src, dst, R, Cc, ld_src, ld_dst, nullptr, nullptr, (hipStream_t)stream);
 }
 hs_status hs_cross_entropy(const float* logits, const int64_t* labels, const float* weight, float label_smoothing,
                            int32_t B, int32_t C, float* loss, float* dlogits, float* row_loss, void* stream) {

@@ -266,6 +266,11 @@ static int gemm_prepare(const hs_gemm_params* p, hipStream_t stream, Prepared& q
         HS_REQUIRE(p->seg_rows <= 0 || (p->rowsum_seg[0] && (p->M <= 2 * p->seg_rows || p->rowsum_seg[1])),
                    "hs_gemm: rowsum_a with seg_rows needs rowsum_seg");
     }
+    if (p->m_rows || p->drop_rows) {
+        HS_REQUIRE(bf16 && combo <= 2 && batch == 1, "hs_gemm: m_rows / drop_rows need a plain bf16 GEMM without batch");
+        a.m_rows = p->m_rows;
+        a.drop_rows = p->drop_rows;
+    }
     a.seg_rows = p->seg_rows;
     a.D_seg[0] = (char*)p->D_seg[0];
     a.D_seg[1] = (char*)p->D_seg[1];
@@ -498,7 +503,7 @@ static int gemm_prepare(const hs_gemm_params* p, hipStream_t stream, Prepared& q
         // (or hs_gemm_debug ablation bit 64).
         static const bool on = [] { const char* e = getenv("HAMSPINE_PERSISTENT"); return e && e[0] == '1'; }();
         static const int cus = [] { hipDeviceProp_t pr; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 256; }();
-        if ((on || (g_dbg_ablate & 64)) && bf16 && split == 1 && batch == 1 && !a.stamps && !p->rowsum_a && !p->bnb_partials && !p->bn_finish && (cfg == CFG_64x64 || cfg == CFG_128x64) &&
+        if ((on || (g_dbg_ablate & 64)) && bf16 && split == 1 && batch == 1 && !a.stamps && !a.m_rows && !a.drop_rows && !p->rowsum_a && !p->bnb_partials && !p->bn_finish && (cfg == CFG_64x64 || cfg == CFG_128x64) &&
             (combo == 0 || combo == 1 || combo == 3 || combo == 4)) {
             const int lds = a.lds_stages * (BM + BN) * 64 * 2;
             const int per_cu = std::max(1, std::min(cfg == CFG_64x64 ? 3 : 2, (160 * 1024) / lds));   // 168 / 256 VGPRs, LDS

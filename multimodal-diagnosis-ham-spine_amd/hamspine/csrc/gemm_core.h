@@ -94,7 +94,13 @@ struct GemmArgs {
     int epi_generic;              // measurement only (hs_gemm_debug bit 32): always take the generic epilogue body
     int dbg;                      // measurement only: the hs_gemm_debug ablation bits
     unsigned long long* stamps;   // measurement only (hs_gemm_debug_stamps): 6 shader-clock stamps per workgroup, else NULL
+    // Packed-row launches (the BERT tower on its valid tokens only, hs_gemm_params.m_rows / drop_rows): the row count
+    // lives in DEVICE memory and the host never reads it, so grids and tile shapes stay those of the padded M / K.  All NULL
+    // (every other caller): today's behaviour.
+    const int* m_rows;            // tokens on M: a workgroup whose tile starts at a row >= *m_rows returns at once
+    const int* drop_rows;         // [M]: the hidden-dropout index of output row m is built from drop_rows[m] (its padded row)
 };
+
 // stamp k of this workgroup: 0 start (clock taken at entry, stored together with stamp 1), 1 first DMA issued, 2 first tile landed (barrier passed), 3 K loop done,
 // 4 epilogue done (stores issued); slot 5 = XCC/CU id bits of HW_ID
 #define HS_STAMP(k)                                                                                              \
@@ -205,8 +211,10 @@ __device__ __forceinline__ unsigned epi_flags(const GemmArgs& a) {
 // DEFER: nothing is stored; v returns the final values and pv the pre-activation copy (EPI_PREACT), for the caller's
 // 16-byte paired stores.
 template <typename T, int CF = -1, bool FULL = false, bool DEFER = false>
+// md: the row the dropout index is built from (packed rows: the row's padded position, which the tiled bodies fetch in front
+// of their K walk); < 0: taken from a.drop_rows / m here.
 __device__ __forceinline__ void epilogue4(const GemmArgs& a, unsigned rt_flags, long long dbase, int z, int m, int n,
-                                          float* v, float* pv = nullptr) {
+                                          float* v, float* pv = nullptr, int md_in = -1) {
     if constexpr (!FULL) {
         if (m >= a.M || n >= a.N) return;
     }
@@ -270,7 +278,10 @@ __device__ __forceinline__ void epilogue4(const GemmArgs& a, unsigned rt_flags, 
         for (int j = 0; j < 4; ++j) v[j] = gelu_fwd_t<T>(v[j]);
     }
     if (fl & EPI_DROP) {
-        const unsigned long long q = ((unsigned long long)z * a.M + m) * (unsigned long long)a.N + n;
+        // packed rows: the draw is the one of the row's padded position (the same mask as the padded tower's)
+        const unsigned long long md = md_in >= 0 ? (unsigned long long)md_in
+                                      : a.drop_rows ? (unsigned long long)((const HS_GLOBAL int*)a.drop_rows)[m] : (unsigned long long)m;
+        const unsigned long long q = ((unsigned long long)z * a.M + md) * (unsigned long long)a.N + n;
         if ((q & 3) == 0) {
             float sc[4];
             dropout_scale4(a.drop_seed, q, a.drop_thresh, a.drop_inv_keep, sc);
@@ -565,7 +576,7 @@ __device__ __forceinline__ int rc_logical_chunk(int k, int pcc) {
 // The epilogue of one workgroup tile for a compile-time feature set CF (or the run-time mask `epi` when CF < 0).
 template <typename T, int CF, bool FULL, int FM, int FN, int WM, int WN>
 __device__ __forceinline__ void run_epilogue(const GemmArgs& a, const unsigned epi, f32x4 (&acc)[FM][FN], int m0, int n0, int wm,
-                                             int wn, int l15, int g, long long d_boff, int z) {
+                                             int wn, int l15, int g, long long d_boff, int z, const int (&mdrop)[FM]) {
         // bf16 results of full tiles: 8-byte stores of the lane-owned 4 columns reach memory as separate partial-sector
         // writes once the epilogue is fast (measured 2.75x the algorithmic write bytes), so two column fragments are
         // exchanged between lane pairs (g, g^1) and every lane stores 8 consecutive columns = 16 bytes: each row gets whole
@@ -581,8 +592,8 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& a, const unsigned e
                     float v0[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
                     float v1[4] = {acc[i][j + 1][0], acc[i][j + 1][1], acc[i][j + 1][2], acc[i][j + 1][3]};
                     float p0[4], p1[4];
-                    epilogue4<T, CF, true, true>(a, epi, d_boff, z, m, n, v0, p0);
-                    epilogue4<T, CF, true, true>(a, epi, d_boff, z, m, n + 16, v1, p1);
+                    epilogue4<T, CF, true, true>(a, epi, d_boff, z, m, n, v0, p0, mdrop[i]);
+                    epilogue4<T, CF, true, true>(a, epi, d_boff, z, m, n + 16, v1, p1, mdrop[i]);
                     const long long didx = d_boff + (long long)m * a.ldd + (odd ? n + 12 : n);
                     auto pair_store = [&](char* base, const float* x0, const float* x1) {
                         const bf16x4 b0 = {(bf16_t)x0[0], (bf16_t)x0[1], (bf16_t)x0[2], (bf16_t)x0[3]};
@@ -609,7 +620,7 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& a, const unsigned e
             for (int j = 0; j < FN; ++j) {
                 const int n = n0 + wn * WN + j * 16 + 4 * g;
                 float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                epilogue4<T, CF, FULL>(a, epi, d_boff, z, m, n, v);
+                epilogue4<T, CF, FULL>(a, epi, d_boff, z, m, n, v, nullptr, mdrop[i]);
                 if (i == 0 && j == 0) HS_STAMP(5);
             }
         }
@@ -886,6 +897,11 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& a, const int bx, 
     }
     int m0, n0;
     const int z = bz;
+    if (a.m_rows) {      // packed rows: nothing below row *m_rows is read by anyone (wave-uniform; before any barrier, ticket or DMA.
+                         // Every workgroup of a split-K tile takes the same exit, so the tile's tickets stay zero)
+        tile_from_block(a, tm, tn, bx);
+        if (tm * BM >= __builtin_amdgcn_readfirstlane(a.m_rows[0])) return;
+    }
 
     long long a_boff = 0, b_boff = 0, d_boff = 0;
     int kbeg = 0, kend = a.K;
@@ -1122,6 +1138,17 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& a, const int bx, 
                     }
                 }
         }
+    }
+    // packed rows: the padded position of each output row (the dropout index) does not depend on this GEMM either -- one int per
+    // lane covers 64 rows of the wave's WM, requested HERE, in front of the K walk; the epilogue takes row i*16 + l15 from its lane
+    constexpr int NDR = (WM + 63) / 64;
+    int drow_v[NDR];
+#pragma unroll
+    for (int j = 0; j < NDR; ++j) drow_v[j] = 0;
+    const bool have_drow = a.drop_rows != nullptr && a.drop_thresh != 0;
+    if (have_drow) {
+#pragma unroll
+        for (int j = 0; j < NDR; ++j) drow_v[j] = ((const HS_GLOBAL int*)a.drop_rows)[min(m0 + wm * WM + j * 64 + lane, a.M - 1)];
     }
     issue_prologue();
     HS_STAMP(1);
@@ -1560,12 +1587,15 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& a, const int bx, 
     // whole tile inside the matrix and 4-wide storable: one of the feature sets the training / inference steps use gets
     // branch-free code; anything else (edge tiles, rare combinations) takes the generic body
     const unsigned epi_e = res_consumed ? (epi & ~(unsigned)EPI_RES_POST) : epi;     // (the sums' rider already added the residual)
+    int mdrop[FM];
+#pragma unroll
+    for (int i = 0; i < FM; ++i) mdrop[i] = have_drow ? __shfl(drow_v[(i * 16) / 64], (i * 16 + l15) & 63, 64) : -1;
     const bool full = !a.epi_generic && (epi & EPI_VEC) && em0 + BM <= argM && en0 + BN <= argN;
     bool done = false;
     const int ze = split_k > 1 ? 0 : z;                       // batch index seen by the epilogue (a split-K launch has no batch)
     if (full) {
         done = true;
-#define HS_EPI_CASE(F) case (F): run_epilogue<T, (F), true, FM, FN, WM, WN>(a, epi_e, acc, em0, en0, wm, wn, l15, g, d_boff, ze); break
+#define HS_EPI_CASE(F) case (F): run_epilogue<T, (F), true, FM, FN, WM, WN>(a, epi_e, acc, em0, en0, wm, wn, l15, g, d_boff, ze, mdrop); break
         const bool v16 = epi_e & EPI_VEC16;
         const unsigned key = epi_e & ~EPI_VEC16;
         if (!v16 && !(key & EPI_OUT_F32)) done = false;      // bf16 rows that cannot take 16-byte stores: generic body
@@ -1587,7 +1617,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& a, const int bx, 
         }
 #undef HS_EPI_CASE
     }
-    if (!done) run_epilogue<T, -1, false, FM, FN, WM, WN>(a, epi_e, acc, em0, en0, wm, wn, l15, g, d_boff, ze);
+    if (!done) run_epilogue<T, -1, false, FM, FN, WM, WN>(a, epi_e, acc, em0, en0, wm, wn, l15, g, d_boff, ze, mdrop);
     HS_STAMP(4);
     if constexpr (BNF && !PS) {
         if (a.bnf_tickets) bnf_handoff<WGM * 128, BN>(a, smem, tid, tm, tn, en0, bnf_drawn);

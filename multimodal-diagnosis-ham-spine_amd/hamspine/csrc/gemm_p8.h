@@ -62,6 +62,8 @@ __device__ __forceinline__ void gemm_bf16_p8_body(const GemmArgs& a, const int b
     int tm, tn;
     tile_from_block(a, tm, tn, bx);
     const int m0 = tm * BM, n0 = tn * BN;
+    // packed rows (GemmArgs.m_rows): a tile below the device-side row count does nothing (wave-uniform, before any barrier or DMA)
+    if (a.m_rows && m0 >= __builtin_amdgcn_readfirstlane(a.m_rows[0])) return;
     const int ntiles = a.K / BK;
     // (A rotated K walk -- each tile starting at a different K tile so that the workgroups sharing an operand panel through
     // one XCD's L2 do not miss on the same lines at the same moment -- was built and measured: 2.0 instead of 1.39 us per K
@@ -126,6 +128,16 @@ __device__ __forceinline__ void gemm_bf16_p8_body(const GemmArgs& a, const int b
             for (int ks = 0; ks < 2; ++ks) bq[q][j][ks] = *(const bf16x8*)(s + kc_off_bf16<BK>(wn * QN + j * 16 + l15, ks * 4 + g));
     };
 
+    // packed rows: the rows' padded positions (dropout index) requested in front of the K walk, one int per lane per 64 rows of WM
+    constexpr int NDR = (WM + 63) / 64;
+    int drow_v[NDR];
+#pragma unroll
+    for (int j = 0; j < NDR; ++j) drow_v[j] = 0;
+    const bool have_drow = a.drop_rows != nullptr && a.drop_thresh != 0;
+    if (have_drow) {
+#pragma unroll
+        for (int j = 0; j < NDR; ++j) drow_v[j] = ((const HS_GLOBAL int*)a.drop_rows)[min(m0 + wm * WM + j * 64 + lane, a.M - 1)];
+    }
     f32x4 acc[FM][FN];
 #pragma unroll
     for (int i = 0; i < FM; ++i)
@@ -292,8 +304,9 @@ __device__ __forceinline__ void gemm_bf16_p8_body(const GemmArgs& a, const int b
     case (F):                                                                                                                 \
         static_for<0, FM>([&](auto ic) {                                                                                      \
             constexpr int i = decltype(ic)::value;                                                                            \
+            const int md1[1] = {have_drow ? __shfl(drow_v[(i * 16) / 64], (i * 16 + l15) & 63, 64) : -1};                         \
             run_epilogue<T, (F), true, 1, FN, 16, WN>(a, epi, *reinterpret_cast<f32x4(*)[1][FN]>(&acc[i]), m0 + wm * WM + i * 16, n0, 0, \
-                                                      wn, l15, g, 0, 0);                                                     \
+                                                      wn, l15, g, 0, 0, md1);                                                \
         });                                                                                                                   \
         break
     switch (key) {

@@ -263,4 +263,12 @@ __device__ __forceinline__ float wave_max(float v) {
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// Packed rows (nrows != NULL; the BERT tower on its valid tokens, hs_bert_desc.pack_rows): only rows < *nrows exist.  The count
+// is read from device memory and clamped to the M the grid and the buffers were sized for (wave-uniform).
+__device__ __forceinline__ long long packed_rows(const int* nrows, long long M) {
+    if (!nrows) return M;
+    const long long t = __builtin_amdgcn_readfirstlane(nrows[0]);
+    return t < 0 ? 0 : (t > M ? M : t);
+}
+
 }  // namespace hs

@@ -493,11 +493,11 @@ template <typename T, int NV>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, T* __restrict__ y,
                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                     long long M, int H, float eps) {
+                                                     long long M, int H, float eps, const int* __restrict__ nrows) {
     constexpr int E = Chunk<T>::N;
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
+    if (row >= packed_rows(nrows, M)) return;
     const int nch = H / E;
     float v[NV][E];
     float sum = 0.f;
@@ -549,8 +549,13 @@ template <typename T, int NV, bool PRE>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, T* __restrict__ dx,
-                                                     float* __restrict__ ws, long long M, int H, T* __restrict__ dxd,
-                                                     unsigned thresh, float inv_keep, unsigned long long seed) {
+                                                     float* __restrict__ ws, long long M_pad, int H, T* __restrict__ dxd,
+                                                     unsigned thresh, float inv_keep, unsigned long long seed,
+                                                     const int* __restrict__ inv) {
+    // packed rows (inv != NULL): the walk is over PADDED rows; row r lives at packed row inv[r] and is left out where inv[r] < 0.
+    // The padded tower's gradient is an exact zero there, so every partial sum below gets the terms it gets in the padded tower, in
+    // the same order, and the dropout draw is that of the padded row.  (A wave without rows still writes its zero partials.)
+    const long long M = M_pad;
     constexpr int E = Chunk<T>::N;
     constexpr int NP = PRE ? 3 : 2;          // partial rows per block: dgamma, dbeta (, bias gradient)
     float dbs[PRE ? NV : 1][E];
@@ -570,8 +575,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
             const int c = lane + 64 * i;
             gm[i][e] = c < nch ? gamma[c * E + e] : 0.f;
         }
-    for (long long row = wid; row < M; row += nw) {
+    for (long long prow = wid; prow < M; prow += nw) {
+        long long row = prow;
+        if (inv) {
+            row = __builtin_amdgcn_readfirstlane(inv[prow]);
+            if (row < 0 || row >= M) continue;                   // (wave-uniform)
+        }
         const float mu = mean[row], rs = rstd[row];
+        const unsigned long long drow = (unsigned long long)prow;
         float g[NV][E], xh[NV][E];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -608,7 +619,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
 #pragma unroll
                             for (int q4 = 0; q4 < E / 4; ++q4) {
                                 float sc[4];
-                                dropout_scale4(seed, (unsigned long long)row * H + (unsigned long long)c * E + 4 * q4, thresh, inv_keep, sc);
+                                dropout_scale4(seed, drow * H + (unsigned long long)c * E + 4 * q4, thresh, inv_keep, sc);
 #pragma unroll
                                 for (int k = 0; k < 4; ++k) o[4 * q4 + k] *= sc[k];
                             }
@@ -703,12 +714,12 @@ static int ln_bwd_blocks(long long M) {
 
 template <typename T>
 static int ln_fwd_t(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
-                    long long M, int H, float eps, hipStream_t s) {
+                    long long M, int H, float eps, hipStream_t s, const int* nrows) {
     constexpr int E = Chunk<T>::N;
     HS_REQUIRE(H % E == 0 && H <= 64 * E * LN_MAXV, "layernorm: H=%d unsupported for this dtype", H);
     // NV = 16-byte chunks per lane (registers scale with it: H = 768 in bf16 needs 2, not the maximum of 4)
     const int nv = ceil_div(H / E, 64);
-#define LN_FWD(NVV) hipLaunchKernelGGL((ln_fwd_kernel<T, NVV>), dim3(ceil_div(M, 4)), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)y, mean, rstd, M, H, eps)
+#define LN_FWD(NVV) hipLaunchKernelGGL((ln_fwd_kernel<T, NVV>), dim3(ceil_div(M, 4)), dim3(256), 0, s, (const T*)x, gamma, beta, (T*)y, mean, rstd, M, H, eps, nrows)
     if (nv <= 1) LN_FWD(1);
     else if (nv == 2) LN_FWD(2);
     else if (nv == 3) LN_FWD(3);
@@ -721,7 +732,7 @@ template <typename T>
 static int ln_bwd_t(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                     void* dx, float* dgamma, float* dbeta, float* ws, long long ws_bytes, long long M, int H,
                     hipStream_t s, bool pre = false, void* dxd = nullptr, float* dbias = nullptr, float p = 0.f,
-                    unsigned long long seed = 0) {
+                    unsigned long long seed = 0, const int* inv = nullptr) {
     constexpr int E = Chunk<T>::N;
     HS_REQUIRE(H % E == 0 && H <= 64 * E * LN_MAXV, "layernorm_bwd: H=%d unsupported for this dtype", H);
     const int blocks = ln_bwd_blocks(M);
@@ -732,7 +743,7 @@ static int ln_bwd_t(const void* dy, const void* x, const float* gamma, const flo
     const float ik = (pre && p > 0.f) ? 1.f / (1.f - p) : 1.f;
 #define LN_BWD(NVV, PRE)                                                                                                  \
     hipLaunchKernelGGL((ln_bwd_kernel<T, NVV, PRE>), dim3(blocks), dim3(256), np * H * sizeof(float), s, (const T*)dy,     \
-                       (const T*)x, gamma, mean, rstd, (T*)dx, ws, M, H, (T*)dxd, th, ik, seed)
+                       (const T*)x, gamma, mean, rstd, (T*)dx, ws, M, H, (T*)dxd, th, ik, seed, inv)
     if (pre) {
         if (nv <= 1) LN_BWD(1, true);
         else if (nv == 2) LN_BWD(2, true);
@@ -751,28 +762,30 @@ static int ln_bwd_t(const void* dy, const void* x, const float* gamma, const flo
     return HS_OK;
 }
 
+// nrows (forward) / inv (backward): packed rows, see packed_rows and ln_bwd_kernel; NULL = every row
 int ln_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
-           long long M, int H, float eps, hipStream_t s) {
+           long long M, int H, float eps, hipStream_t s, const int* nrows) {
     HS_REQUIRE(x && gamma && beta && y, "layernorm: null argument");
-    return dtype == HS_BF16 ? ln_fwd_t<bf16_t>(x, gamma, beta, y, mean, rstd, M, H, eps, s)
-                            : ln_fwd_t<float>(x, gamma, beta, y, mean, rstd, M, H, eps, s);
+    return dtype == HS_BF16 ? ln_fwd_t<bf16_t>(x, gamma, beta, y, mean, rstd, M, H, eps, s, nrows)
+                            : ln_fwd_t<float>(x, gamma, beta, y, mean, rstd, M, H, eps, s, nrows);
 }
 int ln_bwd(int dtype, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-           void* dx, float* dgamma, float* dbeta, float* ws, long long ws_bytes, long long M, int H, hipStream_t s) {
+           void* dx, float* dgamma, float* dbeta, float* ws, long long ws_bytes, long long M, int H, hipStream_t s,
+           const int* inv) {
     HS_REQUIRE(dy && x && gamma && mean && rstd && dgamma && dbeta, "layernorm_bwd: null argument");
-    return dtype == HS_BF16 ? ln_bwd_t<bf16_t>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, ws_bytes, M, H, s)
-                            : ln_bwd_t<float>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, ws_bytes, M, H, s);
+    return dtype == HS_BF16 ? ln_bwd_t<bf16_t>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, ws_bytes, M, H, s, false, nullptr, nullptr, 0.f, 0, inv)
+                            : ln_bwd_t<float>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, ws_bytes, M, H, s, false, nullptr, nullptr, 0.f, 0, inv);
 }
 // LayerNorm backward that also serves the layer in front of it: dx_dropped = dx * dropout mask(p, seed, element index)
 // (p = 0: dx itself; may be NULL) and dbias = column sums of dx_dropped.
 int ln_bwd_pre(int dtype, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx,
                float* dgamma, float* dbeta, void* dx_dropped, float* dbias, float p, unsigned long long seed, float* ws,
-               long long ws_bytes, long long M, int H, hipStream_t s) {
+               long long ws_bytes, long long M, int H, hipStream_t s, const int* inv) {
     HS_REQUIRE(dy && x && gamma && mean && rstd && dgamma && dbeta, "layernorm_bwd_pre: null argument");
     HS_REQUIRE(p >= 0.f && p < 1.f, "layernorm_bwd_pre: bad dropout probability");
     return dtype == HS_BF16
-               ? ln_bwd_t<bf16_t>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, ws_bytes, M, H, s, true, dx_dropped, dbias, p, seed)
-               : ln_bwd_t<float>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, ws_bytes, M, H, s, true, dx_dropped, dbias, p, seed);
+               ? ln_bwd_t<bf16_t>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, ws_bytes, M, H, s, true, dx_dropped, dbias, p, seed, inv)
+               : ln_bwd_t<float>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, ws_bytes, M, H, s, true, dx_dropped, dbias, p, seed, inv);
 }
 long long ln_bwd_ws_bytes(long long M, int H) { return (long long)ln_bwd_blocks(M) * 3 * H * 4; }
 
@@ -784,19 +797,19 @@ hs_status hs_batchnorm_bwd(const hs_bn_bwd_params* p, void* stream) { return hs:
 int64_t hs_batchnorm_ws_bytes(int64_t M, int32_t C, int32_t dtype) { return hs::bn_ws_bytes(M, C, dtype); }
 hs_status hs_layernorm_fwd(int32_t dtype, const void* x, const float* gamma, const float* beta, void* y, float* mean,
                            float* rstd, int64_t M, int32_t H, float eps, void* stream) {
-    return hs::ln_fwd(dtype, x, gamma, beta, y, mean, rstd, M, H, eps, (hipStream_t)stream);
+    return hs::ln_fwd(dtype, x, gamma, beta, y, mean, rstd, M, H, eps, (hipStream_t)stream, nullptr);
 }
 hs_status hs_layernorm_bwd(int32_t dtype, const void* dy, const void* x, const float* gamma, const float* mean,
                            const float* rstd, void* dx, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes,
                            int64_t M, int32_t H, void* stream) {
     return hs::ln_bwd(dtype, dy, x, gamma, mean, rstd, dx, dgamma, dbeta, (float*)ws, ws_bytes, M, H,
-                      (hipStream_t)stream);
+                      (hipStream_t)stream, nullptr);
 }
 hs_status hs_layernorm_bwd_pre(int32_t dtype, const void* dy, const void* x, const float* gamma, const float* mean,
                                const float* rstd, void* dx, float* dgamma, float* dbeta, void* dx_dropped, float* dbias,
                                float dropout_p, uint64_t seed, void* ws, int64_t ws_bytes, int64_t M, int32_t H, void* stream) {
     return hs::ln_bwd_pre(dtype, dy, x, gamma, mean, rstd, dx, dgamma, dbeta, dx_dropped, dbias, dropout_p, seed, (float*)ws,
-                          ws_bytes, M, H, (hipStream_t)stream);
+                          ws_bytes, M, H, (hipStream_t)stream, nullptr);
 }
 int64_t hs_layernorm_bwd_ws_bytes(int64_t M, int32_t H) { return hs::ln_bwd_ws_bytes(M, H); }
 }

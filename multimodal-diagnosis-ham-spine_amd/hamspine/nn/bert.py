@@ -146,8 +146,13 @@ class BertPooler(nn.Module):
 
 
 class BertModel(nn.Module):
-    def __init__(self, config=None, add_pooling_layer=True):
+    """skip_padded_rows (default off): run the tower on the tokens whose attention_mask is non-zero only.  last_hidden_state
+    then holds zeros at masked positions and gradients arriving there are ignored -- for consumers that key-mask the text
+    (hamspine.tower.bert_hidden has the details).  Off, and for every shape the packed kernels do not cover, every row is computed."""
+
+    def __init__(self, config=None, add_pooling_layer=True, skip_padded_rows=False):
         super().__init__()
+        self.skip_padded_rows = bool(skip_padded_rows)
         self.config = config or BertConfig()
         self.embeddings = BertEmbeddings(self.config)
         self.encoder = BertEncoder(self.config)
@@ -164,7 +169,7 @@ class BertModel(nn.Module):
             if attention_mask.dtype != torch.int64:
                 attention_mask = attention_mask.long()
         from .. import tower
-        h = tower.bert_hidden(self, input_ids, attention_mask)      # whole tower in one node (no hooks registered)
+        h = tower.bert_hidden(self, input_ids, attention_mask, self.skip_padded_rows)      # whole tower in one node (no hooks registered)
         if h is None:
             h = self.embeddings(input_ids)
             for layer in self.encoder.layer:
@@ -173,14 +178,14 @@ class BertModel(nn.Module):
 
     # ------------------------------------------------------------------------------------------
     @classmethod
-    def from_pretrained(cls, path, **kw):
+    def from_pretrained(cls, path, skip_padded_rows=False, **kw):
         """Load a *local* HF-format directory (config.json + model.safetensors | pytorch_model.bin).
         Hub names cannot be resolved (no network): raise instead of guessing."""
         if not os.path.isdir(path):
             raise FileNotFoundError(
                 f"BertModel.from_pretrained({path!r}): not a local directory; hub downloads are unavailable")
         config = BertConfig.from_json_file(os.path.join(path, "config.json"))
-        model = cls(config)
+        model = cls(config, skip_padded_rows=skip_padded_rows)
         st_path = os.path.join(path, "model.safetensors")
         bin_path = os.path.join(path, "pytorch_model.bin")
         if os.path.exists(st_path):

@@ -11,6 +11,7 @@ autograd every step, so AccumulateGrad adopts them without a copy); with hamspin
 The per-block modules stay the hookable path: a tower falls back to them whenever any of its submodules carries a hook
 (Grad-CAM: reference scripts/run_analysis.py:126-133).
 """
+import os
 import ctypes as C
 
 import torch
@@ -371,7 +372,7 @@ def _lin(l, in_f, out_f, w, b, dw, db):
 
 
 class _BertEntry:
-    def __init__(self, model, B, Lq, dtype, training, params, needs, device):
+    def __init__(self, model, B, Lq, dtype, training, params, needs, device, pack_rows=False):
         c = model.config
         if len(model.encoder.layer) > L.BERT_MAX_LAYERS:
             raise L.HamspineError(f"hamspine.tower: {len(model.encoder.layer)} BertLayers (max {L.BERT_MAX_LAYERS})")
@@ -390,6 +391,8 @@ class _BertEntry:
         d.word, d.pos, d.type0, d.gamma, d.beta = (p.data_ptr() for p in params[:5])
         d.dword, d.dpos, d.dtype0, d.dgamma, d.dbeta = gp[:5]
         d.n_layers = len(model.encoder.layer)
+        d.pack_rows = 1 if pack_rows else 0
+        self.pack_rows = bool(pack_rows)
         gi = 5
         for i, layer in enumerate(model.encoder.layer):
             ld = d.layers[i]
@@ -437,7 +440,7 @@ class BertTowerFn(Function):
 
     @staticmethod
     def forward(ctx, ids, mask, holder, *params):
-        model, training = holder
+        model, training, pack_rows = holder
         rt.need_gpu(ids, mask, *params)
         ids = ids.contiguous()
         if ids.dtype != torch.int64:
@@ -447,11 +450,12 @@ class BertTowerFn(Function):
             raise ValueError(f"sequence length {Lq} exceeds max_position_embeddings")
         dtype = hamspine.compute_dtype()
         needs = tuple(ctx.needs_input_grad[3:])
-        key = ("bert", B, Lq, dtype, training, needs)
+        pack_rows = bool(pack_rows) and bert_pack_supported(model, B, Lq, dtype, mask, needs)
+        key = ("bert", B, Lq, dtype, training, needs, pack_rows)
         cache = model.__dict__.setdefault(_CACHE_ATTR, {})
         ent = cache.get(key)
         if ent is None or not ent.valid_for(params):
-            ent = cache[key] = _BertEntry(model, B, Lq, dtype, training, params, needs, ids.device)
+            ent = cache[key] = _BertEntry(model, B, Lq, dtype, training, params, needs, ids.device, pack_rows)
         rt.ensure_shadows(ent.shadow_groups)
         saved = torch.empty(ent.saved_bytes, dtype=torch.uint8, device=ids.device)
         ws = rt.workspace(ent.ws_bytes, ids.device)
@@ -514,10 +518,46 @@ def _bert_desc_with_fresh_grads(ent, params, needs, device):
     return d, store.views
 
 
-def bert_hidden(model, input_ids, attention_mask):
-    """last_hidden_state of `model` (hamspine.nn.BertModel) through the tower executor, or None when it does not apply"""
+def bert_pack_supported(model, B, Lq, dtype, mask, needs=None):
+    """whether the tower can run on the valid tokens only (hs_bert_desc.pack_rows): bf16, head dim 64, at most 128 tokens (the
+    packed fused-attention kernels), a mask to take the rows from, the q / k / v weights of a layer all trained or all frozen
+    (their gradients come from one fused GEMM; `needs` = needs_input_grad of bert_params(model)), and the library's latched
+    switches leaving it its kernels (hs_bert_pack_rows_available: asked of the library, so the two sides cannot disagree).
+    HAMSPINE_BERT_PACK=0 forces the padded path (read on every call: it is the A/B switch).  Anything else: the padded tower,
+    silently."""
+    if os.environ.get("HAMSPINE_BERT_PACK", "1") == "0" or mask is None or dtype != torch.bfloat16:
+        return False
+    if not L.lib().hs_bert_pack_rows_available():
+        return False
+    c = model.config
+    H = c.hidden_size
+    if Lq > 128 or (B * Lq) % 8 != 0 or H % 8 != 0:
+        return False
+    if needs is not None:
+        for i in range(len(model.encoder.layer)):
+            qkv = [bool(needs[5 + 16 * i + k]) for k in (0, 2, 4)]
+            if any(qkv) and not all(qkv):
+                return False
+    return all(H == 64 * layer._heads and layer._inter % 8 == 0 for layer in model.encoder.layer)
+
+
+def bert_ran_packed(hidden):
+    """whether the tower call that produced `hidden` (a last_hidden_state that still carries its autograd node) ran on packed
+    rows; None when it did not come from the tower executor"""
+    ent = getattr(getattr(hidden, "grad_fn", None), "ent", None)
+    return getattr(ent, "pack_rows", None)
+
+
+def bert_hidden(model, input_ids, attention_mask, skip_padded_rows=False):
+    """last_hidden_state of `model` (hamspine.nn.BertModel) through the tower executor, or None when it does not apply.
+
+    skip_padded_rows: compute only the tokens whose attention_mask is non-zero (see hs_bert_desc.pack_rows in
+    include/hamspine.h).  The result then holds ZEROS at masked positions and the backward ignores the cotangent there, so only a
+    consumer that never reads those positions (a key-masked attention) may ask for it.  For right-padded masks every dropout draw
+    is the padded path's; for masks with holes the attention-probability draws differ (their index counts keys in packed order).
+    Shapes the packed kernels do not cover take the padded path."""
     if not (towers_enabled() and input_ids.is_cuda and input_ids.dim() == 2):
         return None
     if _has_hooks(model):
         return None
-    return BertTowerFn.apply(input_ids, attention_mask, (model, model.training), *bert_params(model))
+    return BertTowerFn.apply(input_ids, attention_mask, (model, model.training, bool(skip_padded_rows)), *bert_params(model))

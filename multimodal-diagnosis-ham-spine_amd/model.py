@@ -80,7 +80,10 @@ class MultimodalBaselineModel(nn.Module):
         self.global_local_proj = None
         if global_local_enabled and global_local_combine == "concat":
             self.global_local_proj = Linear(hidden_dim * 2, hidden_dim)
-        self.text_encoder = TextEncoder(model_path=text_model_name, feature_dim=text_feature_dim)
+        # FusionModule / MultiScaleFusionModule read the text only as the keys of an attention masked by text_attention_mask, so
+        # the tower need not compute masked positions; the pooled fusions average over all L rows and keep every row
+        self.text_encoder = TextEncoder(model_path=text_model_name, feature_dim=text_feature_dim,
+                                        skip_padded_rows=fusion_type not in _POOLED_FUSIONS)
 
         if fusion_type == "multiscale":
             self.fusion = MultiScaleFusionModule(text_dim=text_feature_dim, hidden_dim=hidden_dim,
