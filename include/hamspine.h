@@ -513,6 +513,65 @@ hs_status hs_window_partition(int32_t dtype, const float* map, void* tokens, int
    the crop of reference ConNexT/models/block/mamba_vision.py:1317-1330,1825-1827.  Also the backward of hs_window_partition. */
 hs_status hs_window_reverse(int32_t dtype, const void* tokens, float* map, int32_t B, int32_t C, int32_t H, int32_t W, int32_t ws,
                             void* stream);
+
+/* ------------------------------------------------------------------------------------------- */
+/* The convolutional half of MambaVision (csrc/mvconv.hip).  Activations are NHWC rows of `dtype` with a channel pitch that
+   is a multiple of 8 (ld = ceil8(C)); lanes C .. ld-1 hold zeros and every entry below that writes an activation writes
+   them as zeros.                                                                                                       */
+/* ------------------------------------------------------------------------------------------- */
+/* y[N][P][Q][ldy] = conv3x3(x[N][H][W][ldx], pad 1, stride 1 | 2) [+ bias[Kout]], P = (H - 1) / stride + 1: the nn.Conv2d(.., 3,
+   stride, 1) of Downsample, PatchEmbed and ConvBlock (reference ConNexT/models/block/mamba_vision.py:1456,1479,1482,1501,1504)
+   as an implicit GEMM on MFMA at channel counts hs_gemm's convolution refuses (any C, Kout with pitches % 8 == 0; bf16 operands
+   with f32 accumulation, or f32).  wf: the compute copy [Kout][3][3][ldx] of hs_conv3x3_pack_filter.  No im2col buffer. */
+hs_status hs_conv3x3_fwd(int32_t dtype, const void* x, const void* wf, const float* bias, void* y, int32_t N, int32_t H, int32_t W, int32_t C,
+                         int32_t ldx, int32_t Kout, int32_t ldy, int32_t stride, void* stream);
+/* dx[N][H][W][lddx] of the above from dy[N][P][Q][lddy], for odd and even H, W (the backward of the convolutions of reference
+   ConNexT/models/block/mamba_vision.py:1456,1479,1482,1501,1504).  wt: the transposed compute copy [C][3][3][lddy]. */
+hs_status hs_conv3x3_dgrad(int32_t dtype, const void* dy, const void* wt, void* dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t lddx,
+                           int32_t Kout, int32_t lddy, int32_t stride, void* stream);
+/* compute copies of a filter parameter w (Kout, C, 3, 3) f32 (reference ConNexT/models/block/mamba_vision.py:1456,1479-1504 keeps
+   nn.Conv2d's layout in the state dict): wf[Kout][3][3][ldc] and, unless NULL, wt[C][3][3][ldk], both of `dtype` with zero pad. */
+hs_status hs_conv3x3_pack_filter(int32_t dtype, const float* w, void* wf, void* wt, int32_t Kout, int32_t C, int32_t ldc, int32_t ldk,
+                                 void* stream);
+/* dw (Kout, C, 3, 3) f32 from the [Kout][3][3][ldc] f32 result of hs_gemm's weight-gradient layout (HS_A_RC x HS_B_CONV over the
+   padded input): the weight gradient in the parameter's shape (reference ConNexT/models/block/mamba_vision.py:1456,1479-1504). */
+hs_status hs_conv3x3_unpack_wgrad(const float* g, float* dw, int32_t Kout, int32_t C, int32_t ldc, void* stream);
+/* image (N, Cin, H, W) f32 -> NHWC rows [N][H][W][ld] of `dtype`, channels Cin .. ld-1 zero: how the image enters PatchEmbed
+   (reference ConNexT/models/block/mamba_vision.py:1487-1490 takes it as NCHW). */
+hs_status hs_pack_image_nhwc(int32_t dtype, const float* x, void* y, int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t ld, void* stream);
+/* the backward of hs_pack_image_nhwc: NHWC rows of `dtype` -> (N, Cin, H, W) f32, the input gradient of PatchEmbed (reference
+   ConNexT/models/block/mamba_vision.py:1487-1490). */
+hs_status hs_unpack_image_nhwc(int32_t dtype, const void* y, float* x, int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t ld, void* stream);
+/* y = gelu_tanh(fma(x, scale, shift)) over [M][ld] rows: norm1 + act1 of ConvBlock (reference
+   ConNexT/models/block/mamba_vision.py:1517-1518); scale / shift from hs_batchnorm_fwd with y = NULL. */
+hs_status hs_bn_gelu_tanh_fwd(int32_t dtype, const void* x, const float* scale, const float* shift, void* y, int64_t M, int32_t C, int32_t ld,
+                              void* stream);
+/* y = res + ls_gamma[c] * rowscale[row / rows_per_sample] * fma(x, scale, shift): norm2, layer scale, stochastic depth and the
+   residual of ConvBlock (reference ConNexT/models/block/mamba_vision.py:1520-1523).  ls_gamma NULL: no layer scale; rowscale
+   NULL: no stochastic depth. */
+hs_status hs_bn_scale_residual_fwd(int32_t dtype, const void* x, const float* scale, const float* shift, const void* res, const float* ls_gamma,
+                                   const float* rowscale, void* y, int64_t M, int32_t C, int32_t ld, int64_t rows_per_sample, void* stream);
+/* backward of the two passes above (mode 0: tanh-GELU, mode 1: layer scale + residual; reference
+   ConNexT/models/block/mamba_vision.py:1517-1523): dx, dgamma, dbeta of the BatchNorm and, mode 1 with ls_gamma, d ls_gamma[c] =
+   bn_gamma[c] sum d' xhat + bn_beta[c] sum d', d' = dy rowscale (the residual's gradient is dy itself).  The pre-BatchNorm
+   gradient is recomputed from x, scale and shift.  One partial-sum pass into ws, a fixed-order final pass, one apply pass.
+   training 0: running statistics, dx = scale * dz. */
+hs_status hs_bn_epilogue_bwd(int32_t dtype, int32_t mode, const void* dy, const void* x, const float* scale, const float* shift,
+                             const float* save_mean, const float* save_invstd, const float* bn_gamma, const float* bn_beta, const float* ls_gamma,
+                             const float* rowscale, void* dx, float* dgamma, float* dbeta, float* dls_gamma, int32_t training, int64_t M, int32_t C,
+                             int32_t ld, int64_t rows_per_sample, void* ws, int64_t ws_bytes, void* stream);
+/* workspace of hs_bn_epilogue_bwd: [row blocks][C][2] partial sums + [C][3] coefficients (reference
+   ConNexT/models/block/mamba_vision.py:1517-1523). */
+int64_t hs_bn_epilogue_ws_bytes(int64_t M, int32_t C);
+/* NHWC map [B][H][W][ld] of `dtype` -> tokens (B nWh nWw, ws ws, C) of `dtype`, zeros for positions right of W / below H: the
+   padding and window_partition of reference ConNexT/models/block/mamba_vision.py:1301-1314,1813-1820 on the Downsample output.
+   Also the backward of hs_window_reverse_nhwc. */
+hs_status hs_window_partition_nhwc(int32_t dtype, const void* map, void* tokens, int32_t B, int32_t C, int32_t ld, int32_t H, int32_t W, int32_t ws,
+                                   void* stream);
+/* tokens -> NHWC map [B][H][W][ld], dropping the tokens of padded positions: window_reverse and the crop of reference
+   ConNexT/models/block/mamba_vision.py:1317-1330,1825-1827.  Also the backward of hs_window_partition_nhwc. */
+hs_status hs_window_reverse_nhwc(int32_t dtype, const void* tokens, void* map, int32_t B, int32_t C, int32_t ld, int32_t H, int32_t W, int32_t ws,
+                                 void* stream);
 /* out[b][t][:] = x[b][t][:] + v[b][:] (v f32): the pooled text feature added to every image token
    (reference modules/fusion_blocks.py:264-292, `image_tokens + txt_feat`). */
 hs_status hs_add_token_bias_fwd(int32_t dtype, const void* x, const float* v, void* out, int32_t B, int32_t L, int32_t H,

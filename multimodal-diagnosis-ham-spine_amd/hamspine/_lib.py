@@ -284,7 +284,20 @@ def _declare(l):
     l.hs_conv1d_same_silu_ws_bytes.restype = i64
     l.hs_window_partition.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
     l.hs_window_reverse.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
-    l.hs_add_token_bias_fwd.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp]
+    l.hs_conv3x3_fwd.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    l.hs_conv3x3_dgrad.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    l.hs_conv3x3_pack_filter.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp]
+    l.hs_conv3x3_unpack_wgrad.argtypes = [vp, vp, i32, i32, i32, vp]
+    l.hs_pack_image_nhwc.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
+    l.hs_unpack_image_nhwc.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
+    l.hs_bn_gelu_tanh_fwd.argtypes = [i32, vp, vp, vp, vp, i64, i32, i32, vp]
+    l.hs_bn_scale_residual_fwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, vp]
+    l.hs_bn_epilogue_bwd.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, i64, vp, i64, vp]
+    l.hs_bn_epilogue_ws_bytes.argtypes = [i64, i32]
+    l.hs_bn_epilogue_ws_bytes.restype = i64
+    l.hs_window_partition_nhwc.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    l.hs_window_reverse_nhwc.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    l.hs_add_token_bias_fwd.argtypes =[i32, vp, vp, vp, i32, i32, i32, vp]
     l.hs_add_token_bias_bwd.argtypes = [i32, vp, vp, i32, i32, i32, vp]
     l.hs_token_seq_assemble_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     l.hs_token_seq_assemble_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
