@@ -381,6 +381,40 @@ hs_status hs_sgd_step_multi(int32_t count, float* const* params, const float* co
                             float grad_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------- */
+/* Muon (csrc/muon.hip): the Muon group of MuonWithAuxAdam, reference scripts/train.py:262-307     */
+/* (`from muon import MuonWithAuxAdam`).  A parameter is the matrix (rows = shape[0], cols = numel  */
+/* / rows) its dense f32 memory holds.  The matrices of one (rows, cols) group are packed into one  */
+/* compute-dtype buffer [count][rows8][cols8], both extents rounded up to a multiple of 8 with zero */
+/* fill, so that every Newton-Schulz product is one batched hs_gemm.  Momentum, norms and the        */
+/* parameter update are f32; every sum is taken in a fixed order (results repeat bitwise).          */
+/* ------------------------------------------------------------------------------------------- */
+#define HS_MUON_MAX 32
+#define HS_MUON_PARTIALS 256
+/* Pre-pass over `count` tensors (reference scripts/train.py:262-307, the momentum / Nesterov / normalise steps of
+   muon_update): m <- m + (1 - beta)(g - m) in place, u = g + beta (m - g), packed[i] = u / (||u||_F + 1e-7) as a
+   [rows8][cols8] matrix of `dtype` with zero fill.  partials: f32 [count][HS_MUON_PARTIALS], the per-workgroup sums of
+   squares, added in index order. */
+hs_status hs_muon_prepare_multi(int32_t dtype, int32_t count, float* const* momentum, const float* const* grads,
+                                void* const* packed, const int32_t* rows, const int32_t* cols, float beta, float* partials,
+                                void* stream);
+/* Five Newton-Schulz iterations X <- a X + (b A + c A A) X, A = X X^T (for rows > cols: on the transpose, read in place),
+   (a, b, c) = (3.4445, -4.7750, 2.0315), on `count` packed matrices X [count][rows8][cols8] of `dtype`, in place (reference
+   scripts/train.py:262-307: zeropower_via_newtonschulz5 of the muon package).  Every product is an hs_gemm launch (batched
+   over the group; split-K for a single matrix): S = b X X^T, B = S + (c / b^2) S S, B += a I, X' = B X.
+   ws: hs_muon_ws_bytes(dtype, count, rows, cols). */
+hs_status hs_muon_orthogonalize(int32_t dtype, int32_t count, int32_t rows, int32_t cols, void* X, void* ws, int64_t ws_bytes,
+                                void* stream);
+/* workspace of hs_muon_orthogonalize (reference scripts/train.py:262-307): S and B [count][n8][n8], n8 = min(rows8, cols8),
+   a second X and, for count == 1, the split-K slabs; -1 for bad arguments. */
+int64_t hs_muon_ws_bytes(int32_t dtype, int32_t count, int32_t rows, int32_t cols);
+/* Apply pass over `count` tensors (reference scripts/train.py:262-307, the update of the Muon group):
+   p <- p (1 - lr weight_decay) - lr scale[i] O, O read from packed[i] ([rows8][cols8] of `dtype`, the pad skipped), and
+   bf16_shadow[i] <- bf16(p) where given (the array or an entry may be NULL), as hs_adam_step_multi_shadow does. */
+hs_status hs_muon_apply_multi(int32_t dtype, int32_t count, float* const* params, void* const* bf16_shadow,
+                              const void* const* packed, const int32_t* rows, const int32_t* cols, const float* scale,
+                              float lr, float weight_decay, void* stream);
+
+/* ------------------------------------------------------------------------------------------- */
 /* small f32 operators at the fusion / head / loss boundary                                       */
 /* ------------------------------------------------------------------------------------------- */
 /* out[b][:] = x[b][t][:] as f32 (CLS pooling, reference modules/fusion_blocks.py:170-173). */

@@ -19,6 +19,7 @@ B_KC, B_RC, B_WDGRAD, B_CONV = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 MUL_NONE, MUL_GELU_GRAD, MUL_RELU_MASK = 0, 1, 2
 CAST_MAX, ADAM_MAX = 48, 32
+MUON_MAX, MUON_PARTIALS = 32, 256
 
 i32, i64, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 
@@ -226,6 +227,11 @@ def _declare(l):
     l.hs_weight_shadow_clear.argtypes = []
     l.hs_weight_shadow_clear.restype = None
     l.hs_sgd_step_multi.argtypes = [i32, P(vp), P(vp), P(vp), P(i64), f32, f32, f32, i32, i32, f32, vp]
+    l.hs_muon_prepare_multi.argtypes = [i32, i32, P(vp), P(vp), P(vp), P(i32), P(i32), f32, vp, vp]
+    l.hs_muon_orthogonalize.argtypes = [i32, i32, i32, i32, vp, vp, i64, vp]
+    l.hs_muon_ws_bytes.argtypes = [i32, i32, i32, i32]
+    l.hs_muon_ws_bytes.restype = i64
+    l.hs_muon_apply_multi.argtypes = [i32, i32, P(vp), P(vp), P(vp), P(i32), P(i32), P(f32), f32, f32, vp]
     l.hs_attention_query.argtypes = [P(AttnDesc), P(i64), P(i64)]
     l.hs_attention_fwd.argtypes = [P(AttnDesc), vp, vp, vp, vp, vp, i64, vp, i64, vp]
     l.hs_attention_bwd.argtypes = [P(AttnDesc), vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp]

@@ -3,6 +3,9 @@
 Drop-in for torch.optim.Adam / AdamW as the reference uses them (scripts/train.py:257-261,
 mibf_net/train_resnet.py:136-139): same hyper-parameters, param_groups (LR schedulers keep working),
 state_dict layout (step / exp_avg / exp_avg_sq).  One launch per 32 tensors instead of torch's foreach chain.
+
+MuonWithAuxAdam (scripts/train.py:262-307, `from muon import MuonWithAuxAdam`): Muon groups on csrc/muon.hip and batched hs_gemm
+Newton-Schulz iterations, auxiliary groups on the same Adam kernel.
 """
 import ctypes as C
 
@@ -206,6 +209,152 @@ class FusedAdamW(_FusedAdamBase):
 
 class FusedAdam(_FusedAdamBase):
     _decoupled = False
+
+
+class MuonWithAuxAdam(_FusedAdamBase):
+    """The optimizer of `configs/ham/ham_optimizer_muon_v1.yml` (reference scripts/train.py:262-307, `from muon import
+    MuonWithAuxAdam`): every param group carries `use_muon`.
+
+    use_muon=True   (lr=0.02, momentum=0.95, weight_decay=0; parameters with ndim >= 2)
+        m <- m + (1-beta)(g-m);  u = g + beta(m-g);  O = NewtonSchulz5(u as (shape[0], -1));
+        p <- p (1 - lr wd) - lr sqrt(max(1, shape[-2] / shape[-1])) O
+      on csrc/muon.hip: one pre-pass and one apply pass over all tensors, and per (rows, cols) shape group ONE
+      hs_muon_orthogonalize call whose fifteen products are batched hs_gemm launches in the compute dtype.
+    use_muon=False  (lr=3e-4, betas=(0.9, 0.95), eps=1e-10, weight_decay=0)
+        Adam with bias correction and decoupled weight decay: _FusedAdamBase._update as it is.
+
+    state_dict layout: momentum_buffer / step, exp_avg, exp_avg_sq.  Parameters without a gradient are skipped (the published
+    package substitutes zeros to keep data-parallel ranks in lock-step; under hamspine.ddp every rank sees every gradient).
+    f32 parameters and gradients only; there is no overlap_backward."""
+    _decoupled = True
+
+    def __init__(self, param_groups):
+        groups = []
+        for g in param_groups:
+            if not isinstance(g, dict) or "use_muon" not in g:
+                raise ValueError("MuonWithAuxAdam: every param group needs a `use_muon` entry")
+            g = dict(g)
+            g["params"] = list(g["params"])
+            if g["use_muon"]:
+                for k, v in (("lr", 0.02), ("momentum", 0.95), ("weight_decay", 0.0)):
+                    g.setdefault(k, v)
+                if any(p.ndim < 2 for p in g["params"]):
+                    raise ValueError("MuonWithAuxAdam: a use_muon group holds a parameter with ndim < 2")
+            else:
+                for k, v in (("lr", 3e-4), ("betas", (0.9, 0.95)), ("eps", 1e-10), ("weight_decay", 0.0)):
+                    g.setdefault(k, v)
+            groups.append(g)
+        torch.optim.Optimizer.__init__(self, groups, dict())
+        self._plans = {}
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            ps = [p for p in group["params"] if p.grad is not None]
+            if not ps:
+                continue
+            if group["use_muon"]:
+                self._muon_update(group, ps)
+            else:
+                self._update(group, ps, 1.0)
+        return loss
+
+    def _muon_plan(self, group, ps, dt):
+        """everything that does not move between steps (the host-cost note of _FusedAdamBase._update applies): shape groups,
+        the packed compute-dtype buffer, pointer tables of parameters / momenta / packed matrices, sizes and scales"""
+        rt.need_gpu(*ps)
+        lib = L.lib()
+        by_shape = {}
+        for p in ps:
+            if p.dtype != torch.float32:
+                raise L.HamspineError("MuonWithAuxAdam expects f32 parameters and gradients")
+            if p.ndim < 2 or p.numel() == 0:
+                raise L.HamspineError("MuonWithAuxAdam: a use_muon parameter needs ndim >= 2 and elements")
+            rows, cols = p.shape[0], p.numel() // p.shape[0]
+            # the parameter's memory is read as it lies, as a (rows, cols) matrix: dense, dimension 0 outermost.  For a
+            # channels_last filter that is a column permutation of the (K, C R S) view, which Newton-Schulz commutes with
+            dense = p.is_contiguous() or (p.ndim == 4 and p.is_contiguous(memory_format=torch.channels_last))
+            if not dense or (rows > 1 and p.stride(0) != cols):
+                raise L.HamspineError("MuonWithAuxAdam: a parameter must be dense with dimension 0 outermost in memory")
+            st = self.state[p]
+            if "momentum_buffer" not in st:
+                st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            by_shape.setdefault((rows, cols), []).append(p)
+        esz = 2 if dt == torch.bfloat16 else 4
+        c8 = lambda v: (v + 7) // 8 * 8
+        order, shapes, offs, off, ws_bytes = [], [], [], 0, 0
+        hs_dt = rt.hs_dtype(dt)
+        for (rows, cols), sel in by_shape.items():
+            shapes.append((rows, cols, len(sel), off))
+            for p in sel:
+                order.append(p)
+                offs.append(off)
+                off += c8(rows) * c8(cols) * esz
+            off = (off + 255) // 256 * 256
+            ws_bytes = max(ws_bytes, int(lib.hs_muon_ws_bytes(hs_dt, len(sel), rows, cols)))
+        n = len(order)
+        dev = order[0].device
+        packed = torch.empty(off, dtype=torch.uint8, device=dev)
+        base = packed.data_ptr()
+        moms = [self.state[p]["momentum_buffer"] for p in order]
+        return {
+            "ids": [id(p) for p in ps], "order": order, "n": n, "dt": dt, "hs_dt": hs_dt, "packed": packed, "shapes": shapes,
+            "ws_bytes": ws_bytes, "partials": torch.empty(n * L.MUON_PARTIALS, dtype=torch.float32, device=dev),
+            "p": (C.c_void_p * n)(*[p.data_ptr() for p in order]), "m": (C.c_void_p * n)(*[m.data_ptr() for m in moms]),
+            "x": (C.c_void_p * n)(*[base + o for o in offs]),
+            "rows": (C.c_int32 * n)(*[p.shape[0] for p in order]),
+            "cols": (C.c_int32 * n)(*[p.numel() // p.shape[0] for p in order]),
+            "scale": (C.c_float * n)(*[max(1.0, p.shape[-2] / p.shape[-1]) ** 0.5 for p in order]),
+            "ptrs": [p.data_ptr() for p in order], "mptrs": [m.data_ptr() for m in moms],
+            "strides": [p.stride() for p in order], "gptrs": None, "garr": None, "shadow_epoch": -1, "h": None}
+
+    def _muon_update(self, group, ps):
+        import hamspine
+        dt = hamspine.compute_dtype()
+        key = (id(group), len(ps), id(ps[0]), id(ps[-1]))
+        pl = self._plans.get(key)
+        if pl is not None:
+            order = pl["order"]
+            state = self.state
+            if (pl["dt"] != dt or pl["ids"] != [id(p) for p in ps] or [p.data_ptr() for p in order] != pl["ptrs"] or
+                    any("momentum_buffer" not in state[p] for p in order) or
+                    [state[p]["momentum_buffer"].data_ptr() for p in order] != pl["mptrs"]):
+                pl = None            # another mode, another parameter set, a re-allocated parameter, a loaded state
+        if pl is None:
+            live = {id(g) for g in self.param_groups}      # load_state_dict replaces the group dicts: let their plans' buffers go
+            self._plans = {k: v for k, v in self._plans.items() if k[0] in live and k != key}
+            pl = self._plans[key] = self._muon_plan(group, ps, dt)
+        order, n = pl["order"], pl["n"]
+        gptrs = [p.grad.data_ptr() for p in order]
+        if gptrs != pl["gptrs"]:
+            for p, st in zip(order, pl["strides"]):
+                g = p.grad
+                if g.dtype != torch.float32:
+                    raise L.HamspineError("MuonWithAuxAdam expects f32 parameters and gradients")
+                if g.stride() != st:    # rare: a gradient produced outside our nodes in another layout
+                    g2 = torch.empty_like(p, memory_format=torch.preserve_format)
+                    g2.copy_(g)
+                    p.grad = g2
+            gptrs = [p.grad.data_ptr() for p in order]
+            pl["gptrs"], pl["garr"] = gptrs, (C.c_void_p * n)(*gptrs)
+        if pl["shadow_epoch"] != rt.shadow_epoch():
+            hp = [rt.shadow_ptr_of(p) for p in order]
+            pl["h"] = (C.c_void_p * n)(*hp) if any(hp) else None
+            pl["shadow_epoch"] = rt.shadow_epoch()
+        lib, s, hs_dt = L.lib(), rt.stream(), pl["hs_dt"]
+        L.check(lib.hs_muon_prepare_multi(hs_dt, n, pl["m"], pl["garr"], pl["x"], pl["rows"], pl["cols"], float(group["momentum"]),
+                                          pl["partials"].data_ptr(), s), "hs_muon_prepare_multi")
+        ws = rt.workspace(pl["ws_bytes"], order[0].device)
+        base = pl["packed"].data_ptr()
+        for rows, cols, count, off in pl["shapes"]:        # one ABI call per shape group
+            L.check(lib.hs_muon_orthogonalize(hs_dt, count, rows, cols, base + off, ws.data_ptr(), ws.numel(), s),
+                    "hs_muon_orthogonalize")
+        L.check(lib.hs_muon_apply_multi(hs_dt, n, pl["p"], pl["h"], pl["x"], pl["rows"], pl["cols"], pl["scale"],
+                                        float(group["lr"]), float(group["weight_decay"]), s), "hs_muon_apply_multi")
 
 
 class FusedSGD(torch.optim.Optimizer):
