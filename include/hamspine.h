@@ -316,6 +316,20 @@ hs_status hs_transpose_bf16(const void* src, void* dst, int32_t R, int32_t C, in
 #define HS_TRANSPOSE_MAX 8
 hs_status hs_transpose_bf16_multi(int32_t count, const void* const* src, void* const* dst, const int32_t* R, const int32_t* C,
                                   const int64_t* ld_src, const int64_t* ld_dst, void* stream);
+/* The row map of the text tower on packed rows (hs_bert_desc.pack_rows), made on the device from attention_mask [B][L]
+   (non-zero = valid) and never read by the host.  int32 words: map[0] = T valid tokens, map[1] = kc_n, map[2] = 32 * kc_n,
+   map[3] = 0; cu = map + 4: [B + 1] first packed row of each sequence; row_of = cu + roundup(B + 1, 4): [B*L] padded position of
+   a packed row; packed_of = row_of + B*L: [B*L] packed row of a padded position or -1; kc_pos = packed_of + B*L:
+   [ceil(B*L / 32)], of which the first kc_n are set: the 32-position chunks of [0, B*L) that hold a valid token, ascending. */
+int64_t hs_bert_row_map_bytes(int32_t B, int32_t L);
+hs_status hs_bert_row_map(const int64_t* mask, int32_t B, int32_t L, int32_t* map, void* stream);
+/* dst [C][ld_dst] = transpose of PACKED token rows src [..][ld_src] (bf16; R = B*L, R, C, ld % 8 == 0): column r is the token at
+   padded position r, read from source row packed_of[r], zeros where that is -1.  With kc_n / kc_pos (both or neither; device
+   pointers into a row map) the columns are chunk-compacted: column c < 32 * *kc_n is padded position kc_pos[c / 32] * 32 + c % 32,
+   columns from there to max(64, roundup(32 * *kc_n, 64)) are zeros and nothing behind that is written.  The form the tower's
+   weight gradients read; exported for tests. */
+hs_status hs_transpose_bf16_tokens(const void* src, void* dst, int32_t R, int32_t C, int64_t ld_src, int64_t ld_dst,
+                                   const int32_t* packed_of, const int32_t* kc_n, const int32_t* kc_pos, void* stream);
 /* out = a*x + b*y (y may be NULL); dtypes are HS_F32/HS_BF16 for inputs (shared) and output. */
 hs_status hs_axpby(int32_t in_dtype, int32_t out_dtype, const void* x, const void* y, void* out, int64_t n, float a,
                    float b, void* stream);
@@ -771,6 +785,14 @@ int32_t hs_measure_build(void);
 /* BertLayer backward (bf16): weight gradients as K-contiguous GEMMs on transposed copies of dY and X (1, default) or straight
    from the row-major operands (0); measurement / A-B testing switch. */
 void hs_set_wgrad_nt(int32_t on);
+/* Text tower on packed rows: the grouped weight gradients walk only the 32-token chunks that hold a valid token (1, default;
+   HAMSPINE_BERT_WGRAD_CHUNKS) or every padded column (0).  Same results bit for bit; measurement / A-B testing switch. */
+void hs_set_bert_wgrad_chunks(int32_t on);
+/* GEMMs with a device-side row count (hs_gemm_params.m_rows): deal the workgroups over the tile rows that hold a row, so the
+   live tiles run on all eight XCDs (1, default; HAMSPINE_PACK_XCD_SPREAD) or over all tile rows (0).  Same results bit for bit. */
+void hs_set_pack_xcd_spread(int32_t on);
+/* number of weight-gradient GEMMs queued so far with a chunk-compacted K walk (process-wide; tests read which path ran) */
+int64_t hs_gemm_k_cols_queued(void);
 
 /* conv + BatchNorm pair of a residual block. `w` is the f32 filter stored KRSC (channels_last). */
 typedef struct hs_conv_bn {
@@ -932,7 +954,9 @@ typedef struct hs_bert_desc {
        keep their order, so holes in a mask are handled like padding; a sequence without valid tokens contributes no rows.
        last_hidden_state is written in the padded [B][L][hidden] layout with ZEROS at masked positions, and the backward
        ignores the cotangent there.  Kernels that sum over tokens (weight / bias / LayerNorm gradients) walk the PADDED positions
-       and leave the masked ones out, where the padded tower adds exact zeros: for right-padded masks every valid hidden state
+       and leave the masked ones out, where the padded tower adds exact zeros (the grouped weight gradients leave out whole
+       32-token chunks without a valid token -- one MFMA each, products of zeros -- and keep the others whole and in order,
+       hs_set_bert_wgrad_chunks): for right-padded masks every valid hidden state
        and every gradient is bitwise what the padded tower computes, dropout draws included.  With holes in a mask the
        attention sums over keys round differently and the attention-probability draws differ (their flat index counts keys
        in packed order). */

@@ -325,6 +325,16 @@ def _declare(l):
     l.hs_measure_build.restype = i32
     l.hs_set_wgrad_nt.argtypes = [i32]
     l.hs_set_wgrad_nt.restype = None
+    l.hs_set_bert_wgrad_chunks.argtypes = [i32]
+    l.hs_set_bert_wgrad_chunks.restype = None
+    l.hs_set_pack_xcd_spread.argtypes = [i32]
+    l.hs_set_pack_xcd_spread.restype = None
+    l.hs_gemm_k_cols_queued.argtypes = []
+    l.hs_gemm_k_cols_queued.restype = i64
+    l.hs_bert_row_map_bytes.argtypes = [i32, i32]
+    l.hs_bert_row_map_bytes.restype = i64
+    l.hs_bert_row_map.argtypes = [vp, i32, i32, vp, vp]
+    l.hs_transpose_bf16_tokens.argtypes = [vp, vp, i32, i32, i64, i64, vp, vp, vp, vp]
     l.hs_bert_pack_rows_available.argtypes = []
     l.hs_bert_pack_rows_available.restype = i32
     l.hs_dwconv_ws_bytes.argtypes = [i32] * 5

@@ -30,7 +30,11 @@ int gemm_bnb_finish_rows(const hs_gemm_params* p);
 void gemm_group_set_immediate_hook(int (*fn)(void*), void* ctx);
 struct GemmGroup;
 GemmGroup* gemm_group_open(hipStream_t s, long long slot);   // slot: any key that is stable across steps (its device table is cached)
-int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s);
+// k_cols (device, or NULL): the operands' K columns are chunk-compacted and the walk ends behind column *k_cols (GemmArgs.k_cols).
+// Only a QUEUED problem can carry it -- one that would be launched on its own is refused -- and gemm_group_takes_k_cols() says
+// beforehand whether K-contiguous bf16 problems are queued at all (they are unless a measurement override is armed).
+int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s, const int* k_cols = nullptr);
+bool gemm_group_takes_k_cols();
 int gemm_group_flush(GemmGroup* g, hipStream_t s);
 bool fused_attention_enabled();
 int attention_bwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, const void* dO, void* dq, void* dk,
@@ -49,7 +53,8 @@ int ln_bwd_pre(int dtype, const void* dy, const void* x, const float* gamma, con
                float* dgamma, float* dbeta, void* dx_dropped, float* dbias, float p, unsigned long long seed, float* ws,
                long long ws_bytes, long long M, int H, hipStream_t s, const int* inv);
 int transpose_bf16_multi_rows(int count, const void* const* src, void* const* dst, const int32_t* R, const int32_t* Cc,
-                              const int64_t* ld_src, const int64_t* ld_dst, const int* inv, const unsigned char* tok, hipStream_t stream);
+                              const int64_t* ld_src, const int64_t* ld_dst, const int* inv, const unsigned char* tok, const int* kc,
+                              const int* kc_pos, hipStream_t stream);
 int colsum_rows(int dtype, const void* x, long long M, int N, int ld, float* out, void* ws, long long ws_bytes, int accumulate,
                 const int* inv, hipStream_t s);
 int dropout_rows(int dtype, const void* x, void* out, long long M, int H, float p, unsigned long long seed, const int* nrows,
@@ -58,7 +63,7 @@ long long bert_row_map_bytes(int B, int L);
 int bert_row_map(const int64_t* mask, int B, int L, int* map, hipStream_t s);
 int bert_unpack_rows(const void* y, void* out, long long rows, long long row_bytes, const int* packed_of, hipStream_t s);
 int bert_pack_rows(const void* dy, void* dst, long long rows, long long row_bytes, const int* nrows, const int* row_of,
-                   hipStream_t s);
+                   const int* word_src, int* word_dst, hipStream_t s);
 int bert_embed_fwd_rows(int dtype, const int64_t* ids, const float* word, const float* pos, const float* type0, const float* gamma,
                         const float* beta, void* sum_out, void* y, float* mean, float* rstd, long long tokens, int L, int H, int V,
                         float eps, float dropout_p, unsigned long long seed, const int* nrows, const int* row_of, hipStream_t stream);
@@ -107,13 +112,21 @@ struct Run {
     GemmGroup* tower_grp = nullptr;
     // ... and the dY^T transposes those GEMMs read: collected here and made by ONE launch in front of the grouped grid (the
     // row-major gradients stay allocated until then) instead of one launch each where the gradient appears
-    struct PendTr { const void* src; void* dst; int R, C; long long ld; bool tok; };
+    struct PendTr { const void* src; void* dst; int R, C; long long ld; unsigned char tok; };   // tok: as transpose_bf16_multi_rows
     std::vector<PendTr> pend_tr;
     // BERT tower on packed rows (hs_bert_desc.pack_rows): the device-side row map.  pk_T -> T, the number of rows that exist (the
     // first T rows of every [B*L][..] buffer); pk_cu [B + 1] first packed row of each sequence; pk_row [B*L] padded row of a packed
     // row; pk_inv [B*L] packed row of a padded row or -1.  All NULL: every row (every other composite, and the padded tower).
     // The host never reads them; M, the grids and the arenas stay those of B*L rows.
     const int *pk_T = nullptr, *pk_cu = nullptr, *pk_row = nullptr, *pk_inv = nullptr;
+    // ... and the 32-token chunks that hold a valid token: pk_kc -> {kc_n, 32 * kc_n}, pk_kcpos [ceil(B*L / 32)] their padded chunk
+    // indices in order.  kc_on (set per BertLayer backward, see there): the layer's transposed token operands are written
+    // chunk-compacted AND its weight-gradient GEMMs end their K walk at *pk_kcols -- the one flag both sides read.  pk_kcols: the
+    // tower backward's copy of pk_kc[1] in ws, made in front of every reader (bert_pack_rows); the grouped grid caches its problem
+    // table between steps and re-uploads it behind a stream synchronise when a pointer in it moves -- ws addresses repeat from
+    // step to step, the caller's saved buffer (where the map lives) does not.
+    const int *pk_kc = nullptr, *pk_kcpos = nullptr, *pk_kcols = nullptr;
+    bool kc_on = false;
 };
 
 // one non-blocking side stream and a ring of events per device (events are re-recordable; every composite joins
@@ -504,7 +517,7 @@ static GemmGroup* open_wgrad_group(hipStream_t s) {
 }
 static bool wgrad_nt_enabled();
 static int linear_wgrad_nt_run(Run& r, const void* xT, const void* dyT, long long M, int in_f, int out_f, float* dw, float* db,
-                               int seg_rows, float* const* dw_seg, float* const* db_seg);
+                               int seg_rows, float* const* dw_seg, float* const* db_seg, const int* k_cols = nullptr);
 static int linear_wgrad_run(Run& r, const void* x, long long M, int ldx, const hs_linear& lin, const void* dy, int ldy) {
     bool db_done = false;
     // bf16, compute-bound shapes (in*out/(in+out) FLOP per operand byte above the ridge; ConvNeXt's 512 <-> 2048 MLPs over
@@ -522,7 +535,7 @@ static int linear_wgrad_run(Run& r, const void* x, long long M, int ldx, const h
         const int32_t R[2] = {(int32_t)M, (int32_t)M}, Cc[2] = {lin.out_f, lin.in_f};
         const int64_t lds[2] = {ldy, ldx}, ldd[2] = {M, M};
         const unsigned char tok[2] = {1, 1};          // packed rows: both operands are token rows, gathered to padded columns
-        CALLK(r, 4, transpose_bf16_multi_rows(2, src, dst, R, Cc, lds, ldd, r.pk_inv, tok, r.s));
+        CALLK(r, 4, transpose_bf16_multi_rows(2, src, dst, R, Cc, lds, ldd, r.pk_inv, tok, nullptr, nullptr, r.s));
         GemmGroup* og = r.plan ? nullptr : open_wgrad_group(r.s);
         const bool keep_flag = r.group_nt;
         GemmGroup* keep_grp = r.grp_nt;
@@ -581,6 +594,15 @@ static bool wgrad_nt_enabled() {             // off: weight gradients from the r
     }
     return g_wgrad_nt == 1;
 }
+// Packed text tower: the grouped weight gradients walk only the 32-token chunks that hold a valid token (Run::kc_on).
+static int g_bert_wgrad_chunks = -1;         // -1: HAMSPINE_BERT_WGRAD_CHUNKS from the environment (default on); hs_set_bert_wgrad_chunks overrides
+static bool bert_wgrad_chunks_enabled() {    // off: every padded column, as the padded tower
+    if (g_bert_wgrad_chunks < 0) {
+        const char* e = getenv("HAMSPINE_BERT_WGRAD_CHUNKS");
+        g_bert_wgrad_chunks = (e && e[0] == '0') ? 0 : 1;
+    }
+    return g_bert_wgrad_chunks == 1;
+}
 static bool grouped_bert_wgrad_enabled() {   // HAMSPINE_GROUPED_BERT_WGRAD=0: every weight-gradient GEMM of a BertLayer on its own
     static int v = -1;
     if (v < 0) {
@@ -604,7 +626,8 @@ static bool deferred_transposes_enabled() {     // HAMSPINE_DEFER_TRANSPOSES=0: 
 // tokens: the rows of src are tokens (packed rows: gathered to their padded columns, zeros at masked positions)
 static int transpose_run(Run& r, const void* src, void* dst, long long R, int Cc, int ld_src, bool for_grouped_wgrad = false,
                          bool tokens = false) {
-    const bool tok = tokens && r.pk_T;
+    // (chunk-compacted only for the layer's own weight-gradient readers, which carry the count: Run::kc_on)
+    const unsigned char tok = (tokens && r.pk_T) ? ((for_grouped_wgrad && r.kc_on) ? 2 : 1) : 0;
     if (for_grouped_wgrad && r.tower_grp && r.group_nt && !r.plan && deferred_transposes_enabled()) {       // its reader is the tower's grouped grid: see pend_tr
         r.pend_tr.push_back(Run::PendTr{src, dst, (int)R, Cc, ld_src, tok});
         return HS_OK;
@@ -614,8 +637,8 @@ static int transpose_run(Run& r, const void* src, void* dst, long long R, int Cc
         void* d1[1] = {dst};
         const int32_t R1[1] = {(int32_t)R}, C1[1] = {Cc};
         const int64_t ls[1] = {ld_src}, ldst[1] = {R};
-        const unsigned char t1[1] = {1};
-        CALLK(r, 4, transpose_bf16_multi_rows(1, s1, d1, R1, C1, ls, ldst, r.pk_inv, t1, r.s));
+        const unsigned char t1[1] = {tok};
+        CALLK(r, 4, transpose_bf16_multi_rows(1, s1, d1, R1, C1, ls, ldst, r.pk_inv, t1, r.pk_kc, r.pk_kcpos, r.s));
         return HS_OK;
     }
     CALLK(r, 4, hs_transpose_bf16(src, dst, (int)R, Cc, ld_src, R, r.s));
@@ -632,15 +655,18 @@ static int pending_transposes_flush(Run& r) {
     for (int i = 0; i < n; ++i) {
         src[i] = r.pend_tr[i].src; dst[i] = r.pend_tr[i].dst; R[i] = r.pend_tr[i].R; Cc[i] = r.pend_tr[i].C;
         lds[i] = r.pend_tr[i].ld; ldd[i] = r.pend_tr[i].R;
-        tok[i] = r.pend_tr[i].tok ? 1 : 0;
+        tok[i] = r.pend_tr[i].tok;
     }
     r.pend_tr.clear();
-    CALLK(r, 4, transpose_bf16_multi_rows(n, src.data(), dst.data(), R.data(), Cc.data(), lds.data(), ldd.data(), r.pk_inv, tok.data(), r.s));
+    CALLK(r, 4, transpose_bf16_multi_rows(n, src.data(), dst.data(), R.data(), Cc.data(), lds.data(), ldd.data(), r.pk_inv, tok.data(), r.pk_kc,
+                                          r.pk_kcpos, r.s));
     return HS_OK;
 }
 // seg: 0 = plain; 3 = fused Q/K/V (lin = the q layer; D_seg / rowsum_seg = k, v)
+// k_cols: xT and dyT are chunk-compacted (Run::kc_on); only the grouped queue can read them
 static int linear_wgrad_nt_run(Run& r, const void* xT, const void* dyT, long long M, int in_f, int out_f, float* dw, float* db,
-                               int seg_rows, float* const* dw_seg, float* const* db_seg) {
+                               int seg_rows, float* const* dw_seg, float* const* db_seg, const int* k_cols) {
+    HS_REQUIRE(!k_cols || r.group_nt, "linear_wgrad_nt: chunk-compacted operands outside a grouped weight-gradient grid");
     hs_gemm_params p = gemm_defaults(r.dt);
     p.a_kind = HS_A_KC; p.b_kind = HS_B_KC;
     p.M = out_f; p.N = in_f; p.K = (int)M;
@@ -662,7 +688,7 @@ static int linear_wgrad_nt_run(Run& r, const void* xT, const void* dyT, long lon
         }
     }
     if (r.group_nt) {                    // no split-K inside a grouped grid: the group fills the chip
-        if (!r.plan && !(knock() & 2)) HS_PROPAGATE(gemm_group_add(r.grp_nt, &p, r.s));
+        if (!r.plan && !(knock() & 2)) HS_PROPAGATE(gemm_group_add(r.grp_nt, &p, r.s, k_cols));
         return HS_OK;
     }
     if (!r.plan && (knock() & 2)) { const int sp = hs_gemm_suggest_split(p.M, p.N, p.K, p.dtype); p.split_k = sp; if (sp > 1) (void)r.ws.alloc(hs_gemm_splitk_ws_bytes(&p)); return HS_OK; }
@@ -1517,6 +1543,13 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
         r.grp_nt = r.tower_grp ? r.tower_grp : gemm_group_open(r.s, (long long)(uintptr_t)d.q.w + 16);
         HS_REQUIRE(r.grp_nt != nullptr, "bert_layer_bwd: cannot set up the grouped weight-gradient launch");
     }
+    // Packed rows, chunk-compacted K.  ONE predicate decides the layout the token transposes below write and the K walk of the
+    // GEMMs that read them: on only when every such reader is a problem queued in the grouped grid (no split-K there; the
+    // queue refuses to launch a problem that carries the count on its own, so a padded-layout reader of a compacted operand,
+    // or the reverse, cannot come about).  Launches through gemm_splitk keep the padded columns: their host-side K split is
+    // part of the summation order.
+    r.kc_on = r.pk_T && r.pk_kcols && grouped && !r.plan && bert_wgrad_chunks_enabled() && gemm_group_takes_k_cols();
+    const int* const k_cols = r.kc_on ? r.pk_kcols : nullptr;
     // X^T of the four saved activations the weight gradients read: all known when the layer's backward starts, so they are
     // transposed by ONE launch (together with the weight copies below) instead of one launch in front of each GEMM
     char* tX_g = nt ? (char*)r.ws.alloc(M * (long long)I * 2) : nullptr;
@@ -1539,7 +1572,7 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
         }
         HS_PROPAGATE(transpose_run(r, dy_rm, tAk, M, lin.out_f, ldy, true, true));
         const bool fused_b = lin.db && (r.group_nt || hs_gemm_suggest_split(lin.out_f, in_f, (int)M, r.dt) <= 1) && fused_bias_grad_enabled();
-        HS_PROPAGATE(linear_wgrad_nt_run(r, xT, tAk, M, in_f, lin.out_f, lin.dw, lin.db, 0, nullptr, nullptr));
+        HS_PROPAGATE(linear_wgrad_nt_run(r, xT, tAk, M, in_f, lin.out_f, lin.dw, lin.db, 0, nullptr, nullptr, k_cols));
         if (lin.db && !fused_b) HS_PROPAGATE(bias_by_colsum(lin, dy_rm, ldy));
         return HS_OK;
     };
@@ -1556,7 +1589,7 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
         unsigned char tok[7];
         int n = 0;
         auto add = [&](const void* s_, void* d_, long long rows, int cols, bool tokens = false) {
-            src[n] = s_; dst[n] = d_; R[n] = (int32_t)rows; Cc[n] = cols; lds[n] = cols; ldd[n] = rows; tok[n] = tokens ? 1 : 0;
+            src[n] = s_; dst[n] = d_; R[n] = (int32_t)rows; Cc[n] = cols; lds[n] = cols; ldd[n] = rows; tok[n] = tokens ? (r.kc_on ? 2 : 1) : 0;
             ++n;
         };
         if (nt) {
@@ -1570,7 +1603,7 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
             add(L.wi, wi_t, I, Hd);
             add(L.wqkv, wqkv_t, 3 * Hd, Hd);
         }
-        if (n > 0) CALLK(r, 4, transpose_bf16_multi_rows(n, src, dst, R, Cc, lds, ldd, r.pk_inv, tok, r.s));
+        if (n > 0) CALLK(r, 4, transpose_bf16_multi_rows(n, src, dst, R, Cc, lds, ldd, r.pk_inv, tok, r.pk_kc, r.pk_kcpos, r.s));
     }
     HS_PROPAGATE(on_side(r, [&]() { return wgrad(L.g, tX_g, I, out_l_w, g2, Hd, tA_ffn2); }));
     HS_PROPAGATE(linear_dgrad_run(r, d.out_l, L.wo, g2, M, Hd, du, I, r.dt, HS_MUL_GELU_GRAD, L.u, I, nullptr, wo_t));
@@ -1609,7 +1642,7 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
                                   fused_bias_grad_enabled();
             float* dws[2] = {d.k.dw, d.v.dw};
             float* dbs[2] = {d.k.db, d.v.db};
-            HS_PROPAGATE(linear_wgrad_nt_run(r, tX_x, tA_qkv, M, Hd, 3 * Hd, d.q.dw, bias_too ? d.q.db : nullptr, Hd, dws, dbs));
+            HS_PROPAGATE(linear_wgrad_nt_run(r, tX_x, tA_qkv, M, Hd, 3 * Hd, d.q.dw, bias_too ? d.q.db : nullptr, Hd, dws, dbs, k_cols));
             if (bias_too) return HS_OK;
             const hs_linear* lins[3] = {&d.q, &d.k, &d.v};
             for (int i = 0; i < 3; ++i) HS_PROPAGATE(bias_by_colsum(*lins[i], dq ? dq + (long long)i * Hd * es : nullptr, 3 * Hd));
@@ -1653,6 +1686,7 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
     }
     if (r.group_nt && !r.plan && !r.tower_grp) HS_PROPAGATE(gemm_group_flush(r.grp_nt, r.s));
     r.group_nt = false;
+    r.kc_on = false;
     HS_PROPAGATE(side_join(r));
     RUN_CHECK_ARENAS(r, "bert_layer_bwd");
     return HS_OK;
@@ -1874,6 +1908,8 @@ static void bert_pack_pointers(Run& r, const hs_bert_desc& d, const BertTowerLay
     r.pk_cu = map + 4;
     r.pk_row = r.pk_cu + (d.B + 1 + 3) / 4 * 4;
     r.pk_inv = r.pk_row + (long long)d.B * d.L;
+    r.pk_kc = map + 1;
+    r.pk_kcpos = r.pk_inv + (long long)d.B * d.L;
 }
 static int bert_check(const hs_bert_desc& d) {
     HS_REQUIRE(d.n_layers >= 0 && d.n_layers <= HS_BERT_MAX_LAYERS, "bert: n_layers %d out of range", d.n_layers);
@@ -1950,6 +1986,7 @@ static int bert_bwd_run(Run& r, const hs_bert_desc& d, const int64_t* ids, const
     const int Hd = d.hidden;
     // packed rows: the cotangent's valid rows are gathered with the forward's map (what arrives at a masked position is ignored)
     char* dy_packed = d.pack_rows ? (char*)r.ws.alloc(lo.act_bytes) : nullptr;
+    int* kcols = d.pack_rows ? (int*)r.ws.alloc(sizeof(int)) : nullptr;      // Run::pk_kcols
     char* gbuf[2] = {(char*)r.ws.alloc(lo.act_bytes), (char*)r.ws.alloc(lo.act_bytes)};
     int cur = 0;
     const void* dy = dy_in;
@@ -1957,7 +1994,8 @@ static int bert_bwd_run(Run& r, const hs_bert_desc& d, const int64_t* ids, const
     if (d.pack_rows && !r.plan) {
         RUN_CHECK_ARENAS(r, "bert_bwd(row map)");
         bert_pack_pointers(r, d, lo);
-        HS_PROPAGATE(bert_pack_rows(dy_in, dy_packed, M, (long long)Hd * esize(d.dtype), r.pk_T, r.pk_row, r.s));
+        HS_PROPAGATE(bert_pack_rows(dy_in, dy_packed, M, (long long)Hd * esize(d.dtype), r.pk_T, r.pk_row, r.pk_kc + 1, kcols, r.s));
+        r.pk_kcols = kcols;
         dy = dy_packed;
     }
     // The K-contiguous weight-gradient GEMMs of `span` consecutive layers run as ONE grouped grid (BERT-base, two layers: 8
@@ -2490,4 +2528,5 @@ int32_t hs_measure_build(void) {
 }
 /* BertLayer weight gradients from transposed (K-contiguous) operands: 1 on (default), 0 = the row-major "tn" form. */
 void hs_set_wgrad_nt(int32_t on) { hs::g_wgrad_nt = on ? 1 : 0; }
+void hs_set_bert_wgrad_chunks(int32_t on) { hs::g_bert_wgrad_chunks = on ? 1 : 0; }
 }

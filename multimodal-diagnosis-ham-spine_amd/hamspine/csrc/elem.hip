@@ -789,12 +789,18 @@ __global__ __launch_bounds__(256) void embed_pos_bwd_kernel(const T* __restrict_
 //   map[0] = T (valid tokens); cu = map + 4: [B + 1] exclusive prefix sum of the valid counts; row_of = cu + roundup(B + 1, 4):
 //   [B*L] padded row b*L + l of packed row t (row_of[t] = t for t >= T, so any index read from it stays inside the buffers);
 //   packed_of = row_of + B*L: [B*L] packed row of a padded row, -1 where the mask is 0.
+//   map[1] = kc_n, map[2] = 32 * kc_n; kc_pos = packed_of + B*L: [ceil(B*L / 32)].  A chunk is 32 consecutive padded positions
+//   of the index space [0, B*L) (not a piece of a sequence: with L % 32 != 0 chunks straddle sequences); kc_n chunks hold at
+//   least one valid token and kc_pos[0 .. kc_n) lists them in ascending order (the weight gradients' compacted K walk, see
+//   transpose_bf16_tile).  Entries at and behind kc_n are not written and not read.
 // One workgroup; a wave per sequence, 64 positions per step (ballot + popcount keep the tokens in order).
 // ============================================================================================
 __global__ __launch_bounds__(256) void bert_row_map_kernel(const long long* __restrict__ mask, int B, int L, int* __restrict__ map) {
+    __shared__ int s_wave_n[4];
     int* cu = map + 4;
     int* row_of = cu + (B + 1 + 3) / 4 * 4;
     int* packed_of = row_of + (long long)B * L;
+    int* kc_pos = packed_of + (long long)B * L;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int b = wave; b < B; b += 4) {                       // pass 1: valid tokens per sequence -> cu[b + 1]
         int n = 0;
@@ -837,6 +843,33 @@ __global__ __launch_bounds__(256) void bert_row_map_kernel(const long long* __re
         }
     }
     for (int t = T + (int)threadIdx.x; t < B * L; t += 256) row_of[t] = t;
+    // the 32-position chunks with a valid token, in order: a chunk per thread, 256 chunks per step (read from the mask itself,
+    // so nothing here waits for pass 2)
+    const int nch = (B * L + 31) / 32;
+    int kc_n = 0;
+    for (int c0 = 0; c0 < nch; c0 += 256) {
+        const int c = c0 + (int)threadIdx.x;
+        long long any = 0;                       // 32 independent loads (clamped address, value dropped behind B*L)
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const long long pos = (long long)c * 32 + i;
+            const long long m = mask[min(pos, (long long)B * L - 1)];
+            any |= pos < (long long)B * L ? m : 0;
+        }
+        const bool v = any != 0;
+        const unsigned long long bal = __ballot(v);
+        if (lane == 0) s_wave_n[wave] = __popcll(bal);
+        __syncthreads();
+        int at = kc_n;
+        for (int w = 0; w < wave; ++w) at += s_wave_n[w];
+        if (v) kc_pos[at + __popcll(bal & ((1ull << lane) - 1ull))] = c;
+        kc_n += s_wave_n[0] + s_wave_n[1] + s_wave_n[2] + s_wave_n[3];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        map[1] = kc_n;
+        map[2] = 32 * kc_n;
+    }
 }
 // last_hidden_state in the padded layout from packed rows, zeros at masked positions: out[row] = packed_of[row] >= 0 ? y[packed_of[row]] : 0
 __global__ __launch_bounds__(256) void bert_unpack_rows_kernel(const u32x4* __restrict__ y, u32x4* __restrict__ out, long long rows, int cpr,
@@ -850,9 +883,14 @@ __global__ __launch_bounds__(256) void bert_unpack_rows_kernel(const u32x4* __re
         out[i] = v;
     }
 }
-// the incoming cotangent's valid rows, packed: dst[t] = dy[row_of[t]] for t < T (what sits at masked positions is ignored)
+// the incoming cotangent's valid rows, packed: dst[t] = dy[row_of[t]] for t < T (what sits at masked positions is ignored).
+// word_dst (optional): *word_dst = *word_src -- the backward's copy of the map's column count (32 * kc_n) at an address that is
+// the same every step, which the cached problem table of the grouped weight-gradient grid needs (the map itself lives in the
+// caller's saved buffer, whose address changes from step to step)
 __global__ __launch_bounds__(256) void bert_pack_rows_kernel(const u32x4* __restrict__ dy, u32x4* __restrict__ dst, long long rows, int cpr,
-                                                             const int* __restrict__ nrows, const int* __restrict__ row_of) {
+                                                             const int* __restrict__ nrows, const int* __restrict__ row_of,
+                                                             const int* __restrict__ word_src, int* __restrict__ word_dst) {
+    if (word_dst && blockIdx.x == 0 && threadIdx.x == 0) word_dst[0] = word_src[0];
     const long long T = packed_rows(nrows, rows), total = T * cpr;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const long long t = i / cpr;
@@ -875,14 +913,34 @@ __global__ __launch_bounds__(256) void bert_pack_rows_kernel(const u32x4* __rest
 // inv (packed rows, else NULL): the source holds PACKED token rows; column r of the result is the token at padded row r, read
 // from source row inv[r], or zeros where inv[r] < 0.  The transposed copy is thus the padded tower's (which holds exact zeros
 // in dY^T at masked positions), so the weight gradient that reads it sums the same terms in the same order.
+// kc (with inv, else NULL; the row map's words 1 .. and its kc_pos): chunk-compacted columns.  Column c of the result is padded
+// position kc_pos[c / 32] * 32 + c % 32 for c < 32 * kc_n: the 32-token chunks that hold no valid token -- exact zeros in the
+// padded copy -- are left out and the others move to the front, whole and in order.  Columns from 32 * kc_n to the end of the
+// last 64-column K tile its reader walks (at least one tile) are zeros; blocks behind that write nothing.  The reader is a
+// grouped weight-gradient grid that ends its K walk there (GemmArgs.k_cols): each of its MFMAs takes one such chunk, so it adds
+// the padded tower's terms in the padded tower's order less products of zeros.  Every index read from the map is clamped: a
+// wrong device value gives wrong numbers, never an address outside the buffers.
 __device__ __forceinline__ void transpose_bf16_tile(const unsigned short* __restrict__ src, unsigned short* __restrict__ dst,
                                                     int R, int Cc, long long lds_, long long ldd, int bx, int by,
-                                                    unsigned (*tile)[33], const int* __restrict__ inv) {
+                                                    unsigned (*tile)[33], const int* __restrict__ inv, const int* __restrict__ kc,
+                                                    const int* __restrict__ kc_pos) {
     const int r0 = by * 64, c0 = bx * 64;
+    const int nch = (R + 31) / 32;
+    int kc_n = 0;
+    if (kc) {
+        kc_n = min(max(__builtin_amdgcn_readfirstlane(kc[0]), 0), nch);
+        if (r0 >= max(64, (32 * kc_n + 63) / 64 * 64)) return;        // block-uniform, before the barrier
+    }
     for (int i = threadIdx.x; i < 512; i += 256) {
         const int r = i >> 3, ch = i & 7;
         u32x4 v = {0u, 0u, 0u, 0u};
         int sr = r0 + r;
+        if (kc) {
+            const int ci = sr >> 5;
+            int pc = ci < kc_n ? kc_pos[ci] : -1;
+            if (pc >= nch) pc = -1;
+            sr = pc >= 0 ? pc * 32 + (sr & 31) : R;                    // R: no such position
+        }
         if (inv && sr < R) {
             sr = inv[sr];
             if (sr >= R) sr = -1;
@@ -909,7 +967,7 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const unsigned shor
                                                              unsigned short* __restrict__ dst, int R, int Cc, long long lds_,
                                                              long long ldd) {
     __shared__ unsigned tile[64][33];
-    transpose_bf16_tile(src, dst, R, Cc, lds_, ldd, blockIdx.x, blockIdx.y, tile, nullptr);
+    transpose_bf16_tile(src, dst, R, Cc, lds_, ldd, blockIdx.x, blockIdx.y, tile, nullptr, nullptr, nullptr);
 }
 // several matrices in one grid (a BertLayer's backward transposes four saved activations and three weight copies before it
 // starts: seven 7 us launches become one)
@@ -922,6 +980,8 @@ struct TransposeTable {
     int count;
     const int* inv;                       // packed rows: packed row of a padded row (-1: none) for the entries in tok_mask
     unsigned tok_mask;                    // bit i: the rows of entry i are packed tokens
+    const int *kc, *kc_pos;               // chunk-compacted columns (kc -> kc_n) for the entries in kc_mask
+    unsigned kc_mask;                     // bit i (a subset of tok_mask): entry i is written chunk-compacted
 };
 __global__ __launch_bounds__(256) void transpose_bf16_multi_kernel(const TransposeTable t) {
     __shared__ unsigned tile[64][33];
@@ -930,7 +990,8 @@ __global__ __launch_bounds__(256) void transpose_bf16_multi_kernel(const Transpo
     const int local = blockIdx.x - t.first[e];
     const int tx = (t.C[e] + 63) / 64;
     const int* inv = (t.inv && ((t.tok_mask >> e) & 1u)) ? t.inv : nullptr;
-    transpose_bf16_tile(t.src[e], t.dst[e], t.R[e], t.C[e], t.ld_src[e], t.ld_dst[e], local % tx, local / tx, tile, inv);
+    transpose_bf16_tile(t.src[e], t.dst[e], t.R[e], t.C[e], t.ld_src[e], t.ld_dst[e], local % tx, local / tx, tile, inv,
+                        (inv && ((t.kc_mask >> e) & 1u)) ? t.kc : nullptr, t.kc_pos);
 }
 
 // ============================================================================================
@@ -1208,9 +1269,11 @@ static int softmax_bwd_t(const float* dP, const void* P, void* dS, long long row
 }
 
 // ---- packed-row entry points (C++ only: the BERT tower executor in blocks.hip) -----------------------------------------------
-// tok[k] != 0: the rows of entry k are packed tokens, gathered to their padded positions through inv (see transpose_bf16_tile)
+// tok[k] != 0: the rows of entry k are packed tokens, gathered to their padded positions through inv (see transpose_bf16_tile);
+// tok[k] == 2: ... and the columns are chunk-compacted through kc / kc_pos (the row map's kc_n word and chunk list; R[k] = B*L)
 int transpose_bf16_multi_rows(int count, const void* const* src, void* const* dst, const int32_t* R, const int32_t* Cc,
-                              const int64_t* ld_src, const int64_t* ld_dst, const int* inv, const unsigned char* tok, hipStream_t stream) {
+                              const int64_t* ld_src, const int64_t* ld_dst, const int* inv, const unsigned char* tok, const int* kc,
+                              const int* kc_pos, hipStream_t stream) {
     HS_REQUIRE(count >= 0 && (count == 0 || (src && dst && R && Cc && ld_src && ld_dst)), "transpose_bf16_multi: bad argument");
     for (int base = 0; base < count; base += HS_TRANSPOSE_MAX) {
         TransposeTable t;
@@ -1230,9 +1293,15 @@ int transpose_bf16_multi_rows(int count, const void* const* src, void* const* ds
             t.first[i] = blocks;
             blocks += ceil_div(Cc[k], 64) * ceil_div(R[k], 64);
             if (inv && tok && tok[k]) t.tok_mask |= 1u << i;
+            if (inv && tok && tok[k] == 2) {
+                HS_REQUIRE(kc && kc_pos, "transpose_bf16_multi: entry %d: chunk-compacted columns need the chunk list", k);
+                t.kc_mask |= 1u << i;
+            }
         }
         t.first[t.count] = blocks;
         t.inv = t.tok_mask ? inv : nullptr;
+        t.kc = t.kc_mask ? kc : nullptr;
+        t.kc_pos = t.kc_mask ? kc_pos : nullptr;
         hipLaunchKernelGGL(transpose_bf16_multi_kernel, dim3(blocks), dim3(256), 0, stream, t);
         HS_LAUNCH_CHECK();
     }
@@ -1258,7 +1327,7 @@ int dropout_rows(int dtype, const void* x, void* out, long long M, int H, float 
     HS_LAUNCH_CHECK();
     return HS_OK;
 }
-long long bert_row_map_bytes(int B, int L) { return (4ll + (B + 1 + 3) / 4 * 4 + 2ll * B * L) * 4; }
+long long bert_row_map_bytes(int B, int L) { return (4ll + (B + 1 + 3) / 4 * 4 + 2ll * B * L + (((long long)B * L + 31) / 32 + 3) / 4 * 4) * 4; }
 int bert_row_map(const int64_t* mask, int B, int L, int* map, hipStream_t s) {
     HS_REQUIRE(mask && map && B > 0 && L > 0, "bert_row_map: bad argument");
     hipLaunchKernelGGL(bert_row_map_kernel, dim3(1), dim3(256), 0, s, (const long long*)mask, B, L, map);
@@ -1274,11 +1343,11 @@ int bert_unpack_rows(const void* y, void* out, long long rows, long long row_byt
     return HS_OK;
 }
 int bert_pack_rows(const void* dy, void* dst, long long rows, long long row_bytes, const int* nrows, const int* row_of,
-                   hipStream_t s) {
-    HS_REQUIRE(dy && dst && nrows && row_of && row_bytes % 16 == 0 && al16(dy, dst), "bert_pack_rows: bad argument");
+                   const int* word_src, int* word_dst, hipStream_t s) {
+    HS_REQUIRE(dy && dst && nrows && row_of && row_bytes % 16 == 0 && al16(dy, dst) && (!word_dst || word_src), "bert_pack_rows: bad argument");
     const int cpr = (int)(row_bytes / 16);
     hipLaunchKernelGGL(bert_pack_rows_kernel, dim3(grid_for(rows * cpr)), dim3(256), 0, s, (const u32x4*)dy, (u32x4*)dst, rows, cpr, nrows,
-                       row_of);
+                       row_of, word_src, word_dst);
     HS_LAUNCH_CHECK();
     return HS_OK;
 }
@@ -1521,7 +1590,20 @@ hs_status hs_transpose_bf16(const void* src, void* dst, int32_t R, int32_t Cc, i
 }
 hs_status hs_transpose_bf16_multi(int32_t count, const void* const* src, void* const* dst, const int32_t* R, const int32_t* Cc,
                                   const int64_t* ld_src, const int64_t* ld_dst, void* stream) {
-    return hs::transpose_bf16_multi_rows(count, src, dst, R, Cc, ld_src, ld_dst, nullptr, nullptr, (hipStream_t)stream);
+    return hs::transpose_bf16_multi_rows(count, src, dst, R, Cc, ld_src, ld_dst, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+hs_status hs_transpose_bf16_tokens(const void* src, void* dst, int32_t R, int32_t Cc, int64_t ld_src, int64_t ld_dst, const int32_t* packed_of,
+                                   const int32_t* kc_n, const int32_t* kc_pos, void* stream) {
+    HS_REQUIRE(packed_of && (kc_n != nullptr) == (kc_pos != nullptr), "hs_transpose_bf16_tokens: bad argument");
+    const void* s1[1] = {src};
+    void* d1[1] = {dst};
+    const int64_t ls[1] = {ld_src}, ldd[1] = {ld_dst};
+    const unsigned char tok[1] = {(unsigned char)(kc_n ? 2 : 1)};
+    return hs::transpose_bf16_multi_rows(1, s1, d1, &R, &Cc, ls, ldd, packed_of, tok, kc_n, kc_pos, (hipStream_t)stream);
+}
+int64_t hs_bert_row_map_bytes(int32_t B, int32_t L) { return (B > 0 && L > 0) ? hs::bert_row_map_bytes(B, L) : 0; }
+hs_status hs_bert_row_map(const int64_t* mask, int32_t B, int32_t L, int32_t* map, void* stream) {
+    return hs::bert_row_map(mask, B, L, map, (hipStream_t)stream);
 }
 hs_status hs_cross_entropy(const float* logits, const int64_t* labels, const float* weight, float label_smoothing,
                            int32_t B, int32_t C, float* loss, float* dlogits, float* row_loss, void* stream) {

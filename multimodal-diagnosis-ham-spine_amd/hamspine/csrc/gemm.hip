@@ -1,4 +1,5 @@
 // host side of the GEMM / implicit-GEMM core: argument checking, tile selection, split-K.
+#include <atomic>
 #include <mutex>
 #include <unordered_set>
 #include <vector>
@@ -177,6 +178,7 @@ static bool bn_finish_variant(int cfg, int combo) {
     return (combo == 0 && (cfg == CFG_64x64 || cfg == CFG_128x64)) || (combo == 3 && (cfg == CFG_64x64 || cfg == CFG_128x64 || cfg == CFG_STEM || cfg == CFG_C3));
 }
 
+static int g_pack_spread = -1;       // packed-row launches: live tiles dealt over all XCDs (gemm_prepare); -1: from the environment
 // everything gemm_impl decides before the launch
 struct Prepared {
     GemmArgs a;
@@ -494,6 +496,15 @@ static int gemm_prepare(const hs_gemm_params* p, hipStream_t stream, Prepared& q
             cnt[{f, p->dtype == HS_BF16 ? 1 : 0}]++;
         }
     }
+    if (a.m_rows) {
+        // packed rows: deal the workgroups over the live tile rows only (tile_from_block).  Unsplit launches without statistics
+        // riders or stamps: there nothing but the tile coordinates depends on the workgroup index.
+        if (g_pack_spread < 0) {        // HAMSPINE_PACK_XCD_SPREAD=0 / hs_set_pack_xcd_spread(0): off
+            const char* e = getenv("HAMSPINE_PACK_XCD_SPREAD");
+            g_pack_spread = (e && e[0] == '0') ? 0 : 1;
+        }
+        a.pack_spread = (g_pack_spread == 1 && split == 1 && !a.colstats && !a.bnb_partials && !a.stamps && cfg != CFG_C3) ? 1 : 0;
+    }
     dim3 grid(a.tiles_m * a.tiles_n, 1, split > 1 ? split : batch);
     {   // persistent launch: more tiles than workgroups the chip holds at once -> one workgroup per resident slot walks
         // several tiles and prefetches the next tile under the current epilogue.  Built, parity-tested and measured: no gain
@@ -719,8 +730,16 @@ static int launch_ungrouped(const hs_gemm_params* p, hipStream_t s) {
     if (g_group_immediate_hook) HS_PROPAGATE(g_group_immediate_hook(g_group_immediate_ctx));
     return gemm_impl(p, s);
 }
-// adds p to the group, or launches it on its own when it cannot be grouped (f32, another layout or tile, no in-launch reduce)
-int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s) {
+// Chunk-compacted K (GemmArgs.k_cols): whether the queue below takes K-contiguous bf16 problems without batch, split-K or
+// statistics (the text tower's weight gradients) into a grid of the 256x128 or the 256x256 phase-pipelined body -- the two bodies
+// that read the count.  It does unless a measurement override (hs_gemm_debug tile override, hs_gemm_debug_stamps) is armed.
+bool gemm_group_takes_k_cols() { return g_dbg_cfg < 0 && !g_dbg_stamps; }
+static std::atomic<long long> g_k_cols_queued{0};      // problems queued with a count (hs_gemm_k_cols_queued: tests read which path ran)
+// adds p to the group, or launches it on its own when it cannot be grouped (f32, another layout or tile, no in-launch reduce).
+// k_cols: see GemmArgs.k_cols.  It exists only inside this queue: hs_gemm_params has no such field, so gemm_impl / gemm_splitk
+// cannot be handed a compacted operand's count, and a problem that carries one is never launched on its own (an error instead).
+int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s, const int* k_cols) {
+    HS_REQUIRE(!k_cols || (g && p && p->a_kind == HS_A_KC && p->b_kind == HS_B_KC), "gemm_group_add: k_cols needs an open group and K-contiguous operands");
     if (!g) return launch_ungrouped(p, s);
     Prepared q;
     const bool big = p->a_kind == HS_A_KC && p->b_kind == HS_B_KC;       // K-contiguous weight gradients: 256x128 tiles
@@ -736,6 +755,7 @@ int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s) {
     const bool ok = big ? (q.bf16 && (q.cfg == CFG_256x128 || q.cfg == CFG_P8_256) && q.combo == 0 && q.batch == 1 && q.split == 1 && !q.a.stamps && !q.a.colstats)
                         : (q.bf16 && q.cfg == CFG_64x64 && (q.combo == 2 || q.combo == 5) && q.batch == 1 && !q.a.stamps &&
                            (q.split == 1 || q.a.tickets != nullptr) && !q.a.rowsum[0] && !q.a.colstats);
+    HS_REQUIRE(!k_cols || ok, "gemm_group_add: a problem with chunk-compacted K columns cannot be queued (gemm_group_takes_k_cols)");
     if (!ok) return launch_ungrouped(p, s);
     const long long ngroups = q.split > 1 ? (q.split + kSplitGroup - 1) / kSplitGroup : 0;
     const long long need = q.split > 1 ? (long long)q.a.tiles_m * q.a.tiles_n * (1 + (ngroups > 1 ? ngroups : 0)) : 0;
@@ -743,7 +763,9 @@ int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s) {
         if (g_group_immediate_hook) HS_PROPAGATE(g_group_immediate_hook(g_group_immediate_ctx));
         HS_PROPAGATE(gemm_group_flush(g, s));
     }
-    if (need > kTicketPool) return launch_ungrouped(p, s);
+    if (need > kTicketPool) return launch_ungrouped(p, s);      // (split-K only: never a problem with k_cols, which is unsplit)
+    q.a.k_cols = k_cols;
+    if (k_cols) g_k_cols_queued.fetch_add(1, std::memory_order_relaxed);
     g->combo = q.combo;
     if (big) {
         g->cfg = q.cfg;
@@ -765,6 +787,8 @@ int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s) {
 extern "C" {
 /* measurement only: device buffer of 6 x (workgroups of the largest launch) uint64, or NULL to switch the stamps off */
 void hs_gemm_debug_stamps(void* device_buffer) { hs::g_dbg_stamps = (unsigned long long*)device_buffer; }
+void hs_set_pack_xcd_spread(int32_t on) { hs::g_pack_spread = on ? 1 : 0; }
+int64_t hs_gemm_k_cols_queued(void) { return hs::g_k_cols_queued.load(std::memory_order_relaxed); }
 void hs_gemm_debug(int32_t cfg_override, int32_t ablate) {
     hs::g_dbg_cfg = cfg_override;
     hs::g_dbg_ablate = ablate;

@@ -99,6 +99,11 @@ struct GemmArgs {
     // (every other caller): today's behaviour.
     const int* m_rows;            // tokens on M: a workgroup whose tile starts at a row >= *m_rows returns at once
     const int* drop_rows;         // [M]: the hidden-dropout index of output row m is built from drop_rows[m] (its padded row)
+    int pack_spread;              // with m_rows: workgroups are mapped onto the LIVE tile rows only (tile_from_block), else onto all
+    // tokens on K (the text tower's weight gradients in a grouped grid, gemm_group_add's k_cols): the operands' columns hold only
+    // the 32-token chunks with a valid token, compacted to the front and zero-filled to the end of the last K tile; the K walk
+    // ends behind column *k_cols (clamped to [one K tile, K]).  Set by the grouped queue alone: no other launch can carry it.
+    const int* k_cols;
 };
 
 // stamp k of this workgroup: 0 start (clock taken at entry, stored together with stamp 1), 1 first DMA issued, 2 first tile landed (barrier passed), 3 K loop done,
@@ -537,19 +542,22 @@ inline long long splitk_slabs(int split) { return split <= kSplitGroup ? split :
 constexpr bool a_is_rc(int k) { return k == HS_A_RC; }
 constexpr bool b_is_rc(int k) { return k != HS_B_KC; }
 
-__device__ __forceinline__ void tile_from_block(const GemmArgs& a, int& tm, int& tn, int bid) {
+// tiles_m: the tile rows the workgroups are dealt over -- a.tiles_m, or fewer for a packed-row launch (GemmArgs.pack_spread: the
+// tile rows that hold a valid token, so that the live tiles go round all eight XCDs instead of filling the first few; the
+// caller returns for bid >= tiles_m * a.tiles_n).  Which workgroup computes a tile changes, not what the tile computes.
+__device__ __forceinline__ void tile_from_block(const GemmArgs& a, int& tm, int& tn, int bid, int tiles_m) {
     // XCD-aware remap: workgroup ids go round-robin over the 8 XCDs, so XCD x is handed the contiguous run of tile
     // ids [x*nwg/8, (x+1)*nwg/8) (bijective for any grid size).  Tile ids walk the output in groups of `group_m` tile
     // rows, m fastest inside a group: the workgroups an XCD runs at one time then cover group_m x (S/group_m) tiles
     // and share group_m A panels and S/group_m B panels through that XCD's L2 (each XCD has its own L2; with plain
     // n-fastest order one XCD streamed the whole B operand once per tile row).
-    const int nwg = a.tiles_m * a.tiles_n;
+    const int nwg = tiles_m * a.tiles_n;
     const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
     const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
     const int gsz = a.group_m * a.tiles_n;
     const int grp = id / gsz;
     const int first_m = grp * a.group_m;
-    const int gm = min(a.group_m, a.tiles_m - first_m);
+    const int gm = min(a.group_m, tiles_m - first_m);
     const int within = id - grp * gsz;
     tn = within / gm;
     tm = first_m + (within - tn * gm);
@@ -897,14 +905,33 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& a, const int bx, 
     }
     int m0, n0;
     const int z = bz;
+    int tiles_m = a.tiles_m;
     if (a.m_rows) {      // packed rows: nothing below row *m_rows is read by anyone (wave-uniform; before any barrier, ticket or DMA.
                          // Every workgroup of a split-K tile takes the same exit, so the tile's tickets stay zero)
-        tile_from_block(a, tm, tn, bx);
-        if (tm * BM >= __builtin_amdgcn_readfirstlane(a.m_rows[0])) return;
+        const int rows = __builtin_amdgcn_readfirstlane(a.m_rows[0]);
+        if (a.pack_spread) {
+            // the live tile rows alone are dealt over the XCDs.  Nothing else in these launches (unsplit, no statistics riders,
+            // no stamps: gemm_prepare) reads the workgroup index: the dropout index comes from the row, the epilogue from (tm, tn)
+            tiles_m = min(tiles_m, max(0, (rows + BM - 1) / BM));
+            if (bx >= tiles_m * a.tiles_n) return;
+        } else {
+            tile_from_block(a, tm, tn, bx, tiles_m);
+            if (tm * BM >= rows) return;
+        }
     }
 
     long long a_boff = 0, b_boff = 0, d_boff = 0;
     int kbeg = 0, kend = a.K;
+    if (a.k_cols) {
+        // Chunk-compacted K (grouped weight gradients of the packed text tower; split_k == 1): the walk ends at the K tile that
+        // holds column *k_cols - 1.  One device word, read once here -- before any barrier or DMA -- and made wave-uniform;
+        // nothing writes it while the launch runs (it is made once per backward, in front of every reader), so every wave of
+        // every workgroup of the tile derives the same ntiles and the counted waits / barriers of the K loop stay in step.
+        // The accumulators (and the ROWSUM ones, which ride the same mma()) take one MFMA per 32-column chunk in column order,
+        // so dropping the all-zero chunks behind *k_cols leaves every f32 sum as it was.
+        const int kc = __builtin_amdgcn_readfirstlane(a.k_cols[0]);
+        kend = min(a.K, max(BK, (kc + BK - 1) / BK * BK));
+    }
     if (a.split_k > 1) {
         kbeg = z * a.k_per_split;
         kend = min(a.K, kbeg + a.k_per_split);
@@ -939,7 +966,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& a, const int bx, 
     // everything that depends on WHICH output tile this workgroup works on (vb = the tile's position in launch order): a
     // persistent launch (a.persist) calls it once per tile
     auto setup_tile = [&](const int vb) {
-    tile_from_block(a, tm, tn, vb);
+    tile_from_block(a, tm, tn, vb, tiles_m);
     m0 = tm * BM;
     n0 = tn * BN;
 #pragma unroll
@@ -1722,7 +1749,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmArgs a) {
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, hh = lane >> 5;
     int tm, tn;
-    tile_from_block(a, tm, tn, blockIdx.x);
+    tile_from_block(a, tm, tn, blockIdx.x, a.tiles_m);
     const int m0 = tm * BM, n0 = tn * BN;
     const int z = blockIdx.z;
 

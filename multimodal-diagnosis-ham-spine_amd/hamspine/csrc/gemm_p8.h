@@ -60,11 +60,26 @@ __device__ __forceinline__ void gemm_bf16_p8_body(const GemmArgs& a, const int b
     const int wm = wave / WGN, wn = wave % WGN;
     const int g = lane >> 4, l15 = lane & 15;
     int tm, tn;
-    tile_from_block(a, tm, tn, bx);
+    // packed rows (GemmArgs.m_rows): a tile below the device-side row count does nothing (wave-uniform, before any barrier or DMA);
+    // with pack_spread the workgroups are dealt over the live tile rows only (tile_from_block)
+    int tiles_m = a.tiles_m;
+    if (a.m_rows && a.pack_spread) {
+        tiles_m = min(tiles_m, max(0, (__builtin_amdgcn_readfirstlane(a.m_rows[0]) + BM - 1) / BM));
+        if (bx >= tiles_m * a.tiles_n) return;
+    }
+    tile_from_block(a, tm, tn, bx, tiles_m);
     const int m0 = tm * BM, n0 = tn * BN;
-    // packed rows (GemmArgs.m_rows): a tile below the device-side row count does nothing (wave-uniform, before any barrier or DMA)
     if (a.m_rows && m0 >= __builtin_amdgcn_readfirstlane(a.m_rows[0])) return;
-    const int ntiles = a.K / BK;
+    // Chunk-compacted K (GemmArgs.k_cols; the grouped weight gradients of the packed text tower): the walk ends at the K tile
+    // that holds column *k_cols - 1, at least one tile, at most all of them.  HAZARD: the barriers and the counted vmcnt waits
+    // below are functions of ntiles, so two waves of a workgroup that disagreed on it would hang, not miscompute.  They cannot:
+    // the count is ONE device word that nothing writes while this launch runs (made once per backward, stream-ordered in front
+    // of every reader: bert_pack_rows_kernel copies it from the row map), it is read once, here, before any barrier or DMA, and readfirstlane makes it
+    // an SGPR, so a wave cannot hold two values of it.  Bitwise: a K tile is two MFMAs per accumulator (ks = 0, 1), each over
+    // 32 consecutive columns, added in column order; the bias row sums (RS, accb) ride the same two MFMAs per tile.  A dropped
+    // chunk would only have added products of exact zeros.
+    int ntiles = a.K / BK;
+    if (a.k_cols) ntiles = max(1, min(ntiles, (__builtin_amdgcn_readfirstlane(a.k_cols[0]) + BK - 1) / BK));
     // (A rotated K walk -- each tile starting at a different K tile so that the workgroups sharing an operand panel through
     // one XCD's L2 do not miss on the same lines at the same moment -- was built and measured: 2.0 instead of 1.39 us per K
     // tile at 4096 x 4096.  Walking in lockstep is what lets the L2 merge the sharers' misses into one fetch.)
