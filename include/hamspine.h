@@ -260,19 +260,26 @@ typedef struct hs_bn_bwd_params {
     int32_t sums_done;
 } hs_bn_bwd_params;
 
+/* Preconditions of both calls: C % 8 == 0 (bf16) / C % 4 == 0 (f32), refused otherwise; every per-channel vector
+   (gamma, beta, running_*, save_*, scale, shift, dgamma, dbeta) is its own 16-byte aligned array -- the apply passes
+   read scale / shift as 16-byte vectors.  A workspace smaller than hs_batchnorm_ws_bytes is refused. */
 hs_status hs_batchnorm_fwd(const hs_bn_params* p, void* stream);
 hs_status hs_batchnorm_bwd(const hs_bn_bwd_params* p, void* stream);
 int64_t hs_batchnorm_ws_bytes(int64_t M, int32_t C, int32_t dtype);
 
 /* LayerNorm over the last dim of [M][H]. Replaces torch.nn.LayerNorm (reference                */
 /* modules/fusion_blocks.py:17-34, modules/heads.py:36; transformers Bert*Output.LayerNorm).    */
+/* Preconditions: H % 8 == 0 and H <= 2048 (bf16) / H % 4 == 0 and H <= 1024 (f32), refused otherwise; M >= 1 (not
+   checked); gamma, beta, dgamma, dbeta, dbias are 16-byte aligned arrays of H floats; mean / rstd (forward) and dx
+   (backward) may be NULL; the backward's workspace holds hs_layernorm_bwd_ws_bytes(M, H) bytes. */
 hs_status hs_layernorm_fwd(int32_t dtype, const void* x, const float* gamma, const float* beta, void* y,
                            float* mean, float* rstd, int64_t M, int32_t H, float eps, void* stream);
 hs_status hs_layernorm_bwd(int32_t dtype, const void* dy, const void* x, const float* gamma, const float* mean,
                            const float* rstd, void* dx, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes,
                            int64_t M, int32_t H, void* stream);
 /* the same, also serving the layer in front of the LayerNorm (BertSelfOutput / BertOutput: y = LN(dropout(dense(h)) + x)):
-   dx_dropped = dx * dropout mask (same (seed, element index) mask as the forward; p = 0: a copy; may be NULL) and
+   dx_dropped = dx * dropout mask (same (seed, element index) mask as the forward, the element index of dx[row][col] being
+   row * H + col, i.e. hs_dropout over the [M][H] tensor; 0 <= p < 1; p = 0: a copy; may be NULL) and
    dbias[H] = column sums of dx_dropped = that dense layer's bias gradient.  Saves the stand-alone dropout and column-sum
    passes of transformers BertSelfOutput / BertOutput backward. */
 hs_status hs_layernorm_bwd_pre(int32_t dtype, const void* dy, const void* x, const float* gamma, const float* mean,
@@ -341,12 +348,16 @@ hs_status hs_relu_bwd(int32_t dtype, const void* dy, const void* y, void* dx, in
 hs_status hs_gelu_bwd(int32_t dtype, const void* dy, const void* u, void* dx, int64_t n, void* stream);
 /* out = x * scalar[0] with the scalar on the device (loss backward without a host sync). */
 hs_status hs_mul_dev_scalar(const float* x, const float* scalar, float* out, int64_t n, void* stream);
-/* out[n] (+)= sum_m x[m*ld + n]  (bias gradients). */
+/* out[n] (+)= sum_m x[m*ld + n]  (bias gradients).  M, N >= 1 (refused otherwise), ld >= N (not checked); ws holds
+   hs_colsum_ws_bytes(M, N) bytes; out[N..] is never written. */
 hs_status hs_colsum(int32_t dtype, const void* x, int64_t M, int32_t N, int32_t ld, float* out, void* ws,
                     int64_t ws_bytes, int32_t accumulate, void* stream);
 int64_t hs_colsum_ws_bytes(int64_t M, int32_t N);
 /* attention probabilities from materialised f32 scores; rows = (b,h,q); mask[b][k] == 0 masks key k.
-   P gets the probabilities (padding columns Lk..ldP-1 zeroed), P_drop (optional) the dropped-out copy. */
+   P gets the probabilities (padding columns Lk..ldP-1 zeroed), P_drop (optional) the dropped-out copy.
+   Preconditions: 1 <= Lk <= ldP <= 1024 (Lk, ldP > 1024 and rows < 1 are refused; ldP >= Lk and ldS, ldG >= Lk are not
+   checked).  The dropout element index of P[r][k] is r * Lk + k (not r * ldP + k): the mask of hs_dropout over a dense
+   [rows][Lk] tensor, in the forward and the backward alike.  A row whose keys are all masked gets the uniform 1 / Lk. */
 hs_status hs_softmax_fwd(int32_t dtype, const float* S, const int64_t* mask, void* P, void* P_drop, int64_t rows,
                          int32_t Lk, int32_t ldS, int32_t ldP, int32_t rows_per_batch, float dropout_p, uint64_t seed,
                          void* stream);

@@ -555,6 +555,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
     // packed rows (inv != NULL): the walk is over PADDED rows; row r lives at packed row inv[r] and is left out where inv[r] < 0.
     // The padded tower's gradient is an exact zero there, so every partial sum below gets the terms it gets in the padded tower, in
     // the same order, and the dropout draw is that of the padded row.  (A wave without rows still writes its zero partials.)
+    // Contraction is off and the fused multiply-adds are written out (fmaf): left to itself the compiler fused the f32
+    // instances without PRE differently from NV = 2 on, so hs_layernorm_bwd and hs_layernorm_bwd_pre gave dx that differed
+    // in the last bit.  What is fused below (dgamma and the two steps of dx; s2 is not) is what every other instance already
+    // compiled to, so their results are bit for bit what they were.
+#pragma clang fp contract(off)
     const long long M = M_pad;
     constexpr int E = Chunk<T>::N;
     constexpr int NP = PRE ? 3 : 2;          // partial rows per block: dgamma, dbeta (, bias gradient)
@@ -595,7 +600,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
                     xh[i][e] = (xv[e] - mu) * rs;
-                    dg[i][e] += g[i][e] * xh[i][e];
+                    dg[i][e] = fmaf(g[i][e], xh[i][e], dg[i][e]);
                     db[i][e] += g[i][e];
                     const float gg = g[i][e] * gm[i][e];
                     s1 += gg;
@@ -612,7 +617,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
                 if (c < nch) {
                     float o[E];
 #pragma unroll
-                    for (int e = 0; e < E; ++e) o[e] = rs * (g[i][e] * gm[i][e] - s1 - xh[i][e] * s2);
+                    for (int e = 0; e < E; ++e) o[e] = rs * fmaf(-xh[i][e], s2, fmaf(g[i][e], gm[i][e], -s1));
                     if (dx) *(u32x4*)(dx + row * H + (long long)c * E) = Chunk<T>::pack(o);
                     if constexpr (PRE) {
                         if (thresh) {
