@@ -1,9 +1,14 @@
-"""ctypes binding of libhamspine_hip.so (the C ABI declared in include/hamspine.h).
+"""ctypes binding of libhamspine_hip.so, derived from the C ABI declared in include/hamspine.h.
+
+The header is the single source of truth: parse_header() reads its constants, structs and prototypes, and this module
+builds the ctypes.Structure classes, the module constants and every entry point's argtypes / restype from that parse.
+A new entry point is declared in the header and nowhere else.
 
 The product path has no CPU fallback: if the shared library is missing, or a tensor that reaches a
 kernel wrapper is not on the HIP device, we raise.  (The CPU oracle lives under /oracle and is only
 used by tests/, bench.py's cpu_baseline leg and __graft_entry__.smoke().)
 """
+import collections
 import ctypes as C
 import os
 import re
@@ -13,359 +18,203 @@ LIB_PATH = os.path.join(_HERE, "libhamspine_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "hamspine.h"))
 
 HS_OK = 0
-HS_F32, HS_BF16 = 0, 1
-A_KC, A_RC, A_CONV, A_DGRAD = 0, 1, 2, 3
-B_KC, B_RC, B_WDGRAD, B_CONV = 0, 1, 2, 3
-ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
-MUL_NONE, MUL_GELU_GRAD, MUL_RELU_MASK = 0, 1, 2
-CAST_MAX, ADAM_MAX = 48, 32
-MUON_MAX, MUON_PARTIALS = 32, 256
-
-i32, i64, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 
 
 class HamspineError(RuntimeError):
     pass
 
 
-class ConvGeom(C.Structure):
-    _fields_ = [(n, i32) for n in (
-        "N", "H", "W", "C", "P", "Q", "K", "R", "S", "stride", "pad",
-        "row_pitch", "img_pitch", "qstep", "no_bounds")]
+# ------------------------------------------------------------------------------------------ the header, parsed
+_SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "hs_status": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+            "float": C.c_float}
+_POINTEES = {"void", "char", "double", "uint8_t", *_SCALARS}
+
+Header = collections.namedtuple("Header", "constants structs prototypes")
 
 
-class GemmParams(C.Structure):
-    _fields_ = [
-        ("dtype", i32), ("a_kind", i32), ("b_kind", i32),
-        ("M", i32), ("N", i32), ("K", i32),
-        ("A", vp), ("B", vp),
-        ("a_elems", i64), ("b_elems", i64),
-        ("lda", i32), ("ldb", i32),
-        ("g", ConvGeom),
-        ("batch", i32), ("batch_inner", i32),
-        ("a_bs0", i64), ("a_bs1", i64), ("b_bs0", i64), ("b_bs1", i64),
-        ("d_bs0", i64), ("d_bs1", i64),
-        ("split_k", i32), ("splitk_ws", vp),
-        ("D", vp), ("ldd", i32), ("out_dtype", i32),
-        ("alpha", f32), ("bias", vp), ("act", i32),
-        ("D_preact", vp), ("residual", vp), ("ldr", i32),
-        ("dropout_p", f32), ("dropout_seed", u64),
-        ("mul_mode", i32), ("mul_src", vp), ("ldm", i32),
-        ("accumulate", i32),
-        ("seg_rows", i32), ("D_seg", vp * 2), ("colscale", vp), ("residual_before_act", i32), ("colstats", vp),
-        ("rowsum_a", vp), ("rowsum_seg", vp * 2),
-        ("bnb_x", vp), ("bnb_scale", vp), ("bnb_shift", vp), ("bnb_mean", vp), ("bnb_invstd", vp), ("bnb_partials", vp),
-        ("bn_finish", vp),
-        ("bnb_y", vp),
-        ("bnb_finish", vp),
-        ("m_rows", vp), ("drop_rows", vp),
-    ]
+def _symbols(text):
+    return sorted(set(re.findall(r"\b(hs_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S))))
 
 
-class BnParams(C.Structure):
-    _fields_ = [
-        ("dtype", i32), ("C", i32), ("M", i64), ("training", i32), ("relu", i32),
-        ("eps", f32), ("momentum", f32),
-        ("x", vp), ("residual", vp), ("y", vp), ("gamma", vp), ("beta", vp),
-        ("running_mean", vp), ("running_var", vp), ("save_mean", vp), ("save_invstd", vp),
-        ("scale", vp), ("shift", vp), ("ws", vp), ("ws_bytes", i64), ("partial_rows", i32),
-        ("stats_done", i32),
-    ]
+def _classify(ctype, structs, what):
+    """(kind, base type name) of a C type spelled without blanks around '*'; kind is one of 'scalar', 'struct', 'struct*',
+    'char*', 'void*' (every other pointer).  Anything else raises."""
+    m = re.fullmatch(r"(const )?(struct )?(\w+)((?:\*(?:const)?)*)", ctype)
+    if m:
+        base, depth = m.group(3), m.group(4).count("*")
+        if depth == 0 and not m.group(2):
+            if base in _SCALARS:
+                return "scalar", base
+            if base in structs:
+                return "struct", base
+        elif depth == 1 and base in structs:
+            return "struct*", base
+        elif ctype == "const char*":
+            return "char*", base
+        elif depth and (m.group(2) or base in _POINTEES or base in structs):
+            return "void*", base
+    raise HamspineError(f"{what}: cannot classify the C type {ctype!r}")
 
 
-class BnBwdParams(C.Structure):
-    _fields_ = [
-        ("dtype", i32), ("C", i32), ("M", i64), ("training", i32), ("relu", i32),
-        ("dy", vp), ("y", vp), ("x", vp), ("gamma", vp), ("save_mean", vp), ("save_invstd", vp),
-        ("dx", vp), ("dres", vp), ("dgamma", vp), ("dbeta", vp), ("ws", vp), ("ws_bytes", i64),
-        ("scale", vp), ("shift", vp), ("partial_rows", i32), ("sums_done", i32),
-    ]
+def _declarator(text, what, typed):
+    """(C type, name, array length as written or None) of `type name[len]`, or of a further `name[len]` after a comma"""
+    m = re.fullmatch((r"(.+?)\b" if typed else "()") + r"(\w+)(?:\[(\w+)\])?", text)
+    if not m:
+        raise HamspineError(f"{what}: cannot read the declarator {text!r}")
+    return m[1].strip(), m[2], m[3]
 
 
-class AttnDesc(C.Structure):
-    _fields_ = [
-        ("dtype", i32), ("B", i32), ("H", i32), ("Lq", i32), ("Lk", i32), ("hd", i32),
-        ("q_bs", i64), ("k_bs", i64), ("v_bs", i64), ("o_bs", i64),
-        ("q_ld", i32), ("k_ld", i32), ("v_ld", i32), ("o_ld", i32),
-        ("scale", f32), ("dropout_p", f32), ("seed", u64), ("key_mask", vp),
-    ]
+def parse_header(text):
+    """Header(constants, structs, prototypes) of the C ABI declared in `text`:
+         constants   {name: int} of every enumerator and every `#define HS_NAME <int>`
+         structs     {name: [(field, C type, array length or None), ...]} in declaration order
+         prototypes  {name: (return C type, [parameter C types])}
+    Strict: a declaration that is not understood raises HamspineError and nothing is skipped."""
+    names = _symbols(text)
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(HS_\w+)(.*)$", text, flags=re.M):
+        if not re.fullmatch(r"\s+-?\d+\s*", value):
+            raise HamspineError(f"#define {name}{value}: not an integer constant")
+        constants[name] = int(value)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    text = re.sub(r" ?\* ?", "*", " ".join(text.split()))
+    structs, prototypes = {}, {}
+    decl = re.compile(r"([^;{}]*)(?:\{([^{}]*)\}([^;{}]*))?;")
+    if decl.sub("", text).strip():
+        raise HamspineError(f"header: no declaration in {decl.sub('', text).strip()[:80]!r}")
+    for m in decl.finditer(text):
+        head, body, tail = (s if s is None else s.strip() for s in m.groups())
+        what = m[0].strip()[:100]
+        proto = re.fullmatch(r"(.+?)\b(hs_\w+) ?\((.*)\)", head)
+        alias = re.fullmatch(r"typedef (\w+) (\w+)", head)
+        if body is None and proto:
+            ret, params = proto[1].strip(), [] if proto[3] == "void" else proto[3].split(",")
+            if ret != "void" and _classify(ret, {}, what)[0] not in ("scalar", "char*"):
+                raise HamspineError(f"{what}: unsupported return type {ret!r}")
+            types = [_declarator(a.strip(), what, True) for a in params]
+            if any(n is not None or _classify(t, structs, what)[0] == "struct" for t, _, n in types):
+                raise HamspineError(f"{what}: array or by-value struct parameter")
+            prototypes[proto[2]] = (ret, [t for t, _, _ in types])
+        elif body is None and alias:                         # a scalar alias the type table already knows
+            if alias[1] not in _SCALARS or _SCALARS.get(alias[2]) is not _SCALARS[alias[1]]:
+                raise HamspineError(f"{what}: typedef the type table does not know")
+        elif body is None and re.fullmatch(r"struct \w+", head):
+            pass                                             # forward declaration: declares no layout
+        elif body is not None and head == "enum" and not tail:
+            for e in body.split(","):
+                e = re.fullmatch(r"(HS_\w+) = (-?\d+)", e.strip())
+                if not e:
+                    raise HamspineError(f"{what}: enumerator without an integer value")
+                constants[e[1]] = int(e[2])
+        elif body is not None and head == "typedef struct " + tail:
+            fields = []
+            for line in filter(None, (s.strip() for s in body.split(";"))):
+                first, *more = (d.strip() for d in line.split(","))
+                ctype = _declarator(first, what, True)[0]
+                _classify(ctype, structs, what)
+                for _, name, length in [_declarator(first, what, True)] + [_declarator(d, what, False) for d in more]:
+                    n = None if length is None else int(length) if length.isdigit() else constants.get(length)
+                    if length is not None and n is None:
+                        raise HamspineError(f"{what}: array length {length!r} is neither a number nor a known #define")
+                    fields.append((name, ctype, n))
+            structs[tail] = fields
+        else:
+            raise HamspineError(f"{what}: not a prototype, enum, scalar typedef or `typedef struct hs_x {{ ... }} hs_x`")
+    if sorted(prototypes) != names:
+        raise HamspineError(f"header: the parsed prototypes and the hs_*( names differ in {set(prototypes) ^ set(names)}")
+    return Header(constants, structs, prototypes)
 
 
-class ConvBn(C.Structure):
-    _fields_ = [
-        ("Cin", i32), ("Cout", i32), ("R", i32), ("stride", i32), ("pad", i32),
-        ("w", vp), ("gamma", vp), ("beta", vp), ("running_mean", vp), ("running_var", vp),
-        ("dw", vp), ("dgamma", vp), ("dbeta", vp),
-    ]
+def _ctype(ctype, classes, param):
+    kind, base = _classify(ctype, classes, ctype)
+    if kind == "scalar":
+        return _SCALARS[base]
+    if kind == "struct":
+        return classes[base]
+    if kind == "struct*" and param:
+        return C.POINTER(classes[base])
+    return C.c_char_p if kind == "char*" else C.c_void_p
 
 
-class ResblockDesc(C.Structure):
-    _fields_ = [
-        ("dtype", i32), ("N", i32), ("H", i32), ("W", i32), ("training", i32),
-        ("eps", f32), ("momentum", f32), ("n_main", i32), ("main", ConvBn * 3),
-        ("has_ds", i32), ("ds", ConvBn), ("inference", i32),
-    ]
+def exported_symbols():
+    """Names declared in include/hamspine.h (used by the CPU-side ABI test)."""
+    return _symbols(open(HEADER_PATH).read())
 
 
-class StemDesc(C.Structure):
-    _fields_ = [
-        ("dtype", i32), ("N", i32), ("H", i32), ("W", i32), ("training", i32),
-        ("eps", f32), ("momentum", f32), ("cb", ConvBn), ("inference", i32),
-    ]
+_header = parse_header(open(HEADER_PATH).read())
+
+# ------------------------------------------------------------------------------------------ structs and constants
+# C struct -> Python name, in the numbering of hs_abi_sizeof
+_STRUCT_NAMES = {
+    "hs_conv_geom": "ConvGeom",
+    "hs_gemm_params": "GemmParams",
+    "hs_bn_params": "BnParams",
+    "hs_bn_bwd_params": "BnBwdParams",
+    "hs_attn_desc": "AttnDesc",
+    "hs_conv_bn": "ConvBn",
+    "hs_resblock_desc": "ResblockDesc",
+    "hs_stem_desc": "StemDesc",
+    "hs_linear": "Linear",
+    "hs_norm": "Norm",
+    "hs_bert_layer_desc": "BertLayerDesc",
+    "hs_resnet_desc": "ResnetDesc",
+    "hs_resnet_plan": "ResnetPlan",
+    "hs_bert_desc": "BertDesc",
+}
+if set(_header.structs) != set(_STRUCT_NAMES):
+    raise HamspineError(f"{HEADER_PATH}: structs without a Python name, or the reverse: {set(_header.structs) ^ set(_STRUCT_NAMES)}")
+_classes = {}
+for _c, _fields in _header.structs.items():
+    _classes[_c] = type(_STRUCT_NAMES[_c], (C.Structure,), {"_fields_": [
+        (f, _ctype(t, _classes, False) * n if n else _ctype(t, _classes, False)) for f, t, n in _fields]})
+globals().update({_STRUCT_NAMES[_c]: _cls for _c, _cls in _classes.items()})
 
 
-class Linear(C.Structure):
-    _fields_ = [("in_f", i32), ("out_f", i32), ("w", vp), ("b", vp), ("dw", vp), ("db", vp)]
+def abi_structs():
+    """(number for hs_abi_sizeof, ctypes mirror) of every struct of the C ABI"""
+    return list(enumerate(_classes[c] for c in _STRUCT_NAMES))
 
 
-class Norm(C.Structure):
-    _fields_ = [("gamma", vp), ("beta", vp), ("dgamma", vp), ("dbeta", vp)]
+def _const(*names):
+    return [_header.constants["HS_" + n] for n in names]
 
 
-class BertLayerDesc(C.Structure):
-    _fields_ = [
-        ("dtype", i32), ("B", i32), ("L", i32), ("hidden", i32), ("heads", i32), ("inter", i32),
-        ("ln_eps", f32), ("hidden_dropout", f32), ("attn_dropout", f32), ("seed", u64),
-        ("attention_mask", vp),
-        ("q", Linear), ("k", Linear), ("v", Linear), ("ao", Linear), ("ln1", Norm),
-        ("inter_l", Linear), ("out_l", Linear), ("ln2", Norm),
-    ]
+if _const("OK") != [HS_OK]:
+    raise HamspineError("HS_OK of the header is not 0")
+HS_F32, HS_BF16 = _const("F32", "BF16")
+A_KC, A_RC, A_CONV, A_DGRAD = _const("A_KC", "A_RC", "A_CONV", "A_DGRAD")
+B_KC, B_RC, B_WDGRAD, B_CONV = _const("B_KC", "B_RC", "B_WDGRAD", "B_CONV")
+ACT_NONE, ACT_RELU, ACT_GELU = _const("ACT_NONE", "ACT_RELU", "ACT_GELU")
+MUL_NONE, MUL_GELU_GRAD, MUL_RELU_MASK = _const("MUL_NONE", "MUL_GELU_GRAD", "MUL_RELU_MASK")
+CAST_MAX, ADAM_MAX, MUON_MAX, MUON_PARTIALS = _const("CAST_MAX", "ADAM_MAX", "MUON_MAX", "MUON_PARTIALS")
+RESNET_MAX_BLOCKS, RESNET_MAX_TAPS, BERT_MAX_LAYERS = _const("RESNET_MAX_BLOCKS", "RESNET_MAX_TAPS", "BERT_MAX_LAYERS")
 
-
-RESNET_MAX_BLOCKS, RESNET_MAX_TAPS, BERT_MAX_LAYERS = 24, 4, 24
-
-
-class ResnetDesc(C.Structure):
-    _fields_ = [("stem", StemDesc), ("n_blocks", i32), ("blocks", ResblockDesc * RESNET_MAX_BLOCKS), ("n_taps", i32),
-                ("tap_block", i32 * RESNET_MAX_TAPS)]
-
-
-class ResnetPlan(C.Structure):
-    _fields_ = [("saved_bytes", i64), ("ws_bytes", i64), ("tap_offset", i64 * RESNET_MAX_TAPS),
-                ("tap_C", i32 * RESNET_MAX_TAPS), ("tap_H", i32 * RESNET_MAX_TAPS), ("tap_W", i32 * RESNET_MAX_TAPS)]
-
-
-class BertDesc(C.Structure):
-    _fields_ = [
-        ("dtype", i32), ("B", i32), ("L", i32), ("hidden", i32), ("vocab", i32), ("max_pos", i32), ("n_types", i32),
-        ("pad_id", i32), ("ln_eps", f32), ("embed_dropout", f32), ("seed", u64),
-        ("word", vp), ("pos", vp), ("type0", vp), ("gamma", vp), ("beta", vp),
-        ("dword", vp), ("dpos", vp), ("dtype0", vp), ("dgamma", vp), ("dbeta", vp),
-        ("n_layers", i32), ("layers", BertLayerDesc * BERT_MAX_LAYERS),
-        ("pack_rows", i32),
-    ]
-
-
+# ------------------------------------------------------------------------------------------ the library
 _lib = None
 
 
 def lib():
-    """Load the shared library once; fail loudly when it has not been built."""
+    """Load the shared library once and type every entry point of the header; fail loudly when it has not been built."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise HamspineError(
                 f"{LIB_PATH} not found: build it with `python __graft_entry__.py build` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-        _lib = C.CDLL(LIB_PATH)
-        _declare(_lib)
+        l = C.CDLL(LIB_PATH)
+        missing = [n for n in _header.prototypes if not hasattr(l, n)]
+        if missing:
+            raise HamspineError(f"{LIB_PATH} lacks declared symbols: {missing}")
+        for n, (ret, params) in _header.prototypes.items():
+            getattr(l, n).restype = None if ret == "void" else _ctype(ret, _classes, True)
+            getattr(l, n).argtypes = [_ctype(t, _classes, True) for t in params]
+        _lib = l
     return _lib
-
-
-def _declare(l):
-    P = C.POINTER
-    l.hs_last_error.restype = C.c_char_p
-    l.hs_gemm.argtypes = [P(GemmParams), vp]
-    l.hs_gemm_splitk_ws_bytes.argtypes = [P(GemmParams)]
-    l.hs_gemm_splitk_ws_bytes.restype = i64
-    l.hs_gemm_stat_rows.argtypes = [P(GemmParams)]
-    l.hs_gemm_bn_finish_rows.argtypes = [P(GemmParams)]
-    l.hs_gemm_bn_finish_rows.restype = i32
-    l.hs_gemm_bnb_finish_rows.argtypes = [P(GemmParams)]
-    l.hs_gemm_bnb_finish_rows.restype = i32
-    l.hs_gemm_tile_rows.argtypes = [P(GemmParams)]
-    l.hs_gemm_tile_rows.restype = i32
-    l.hs_gemm_suggest_split.argtypes = [i32] * 4
-    l.hs_batchnorm_fwd.argtypes = [P(BnParams), vp]
-    l.hs_batchnorm_bwd.argtypes = [P(BnBwdParams), vp]
-    l.hs_batchnorm_ws_bytes.argtypes = [i64, i32, i32]
-    l.hs_batchnorm_ws_bytes.restype = i64
-    l.hs_layernorm_fwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, i64, i32, f32, vp]
-    l.hs_layernorm_bwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, vp]
-    l.hs_layernorm_bwd_pre.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, u64, vp, i64, i64, i32, vp]
-    l.hs_layernorm_bwd_ws_bytes.argtypes = [i64, i32]
-    l.hs_layernorm_bwd_ws_bytes.restype = i64
-    l.hs_maxpool_fwd.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    l.hs_maxpool_bwd.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    l.hs_mean_tokens_fwd.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp]
-    l.hs_mean_tokens_bwd.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp]
-    l.hs_pack_image.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    l.hs_pack_stem_weight.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp]
-    l.hs_unpack_stem_wgrad.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-    l.hs_cast_f32_to_bf16_multi.argtypes = [i32, P(vp), P(vp), P(i64), vp]
-    l.hs_axpby.argtypes = [i32, i32, vp, vp, vp, i64, f32, f32, vp]
-    l.hs_transpose_bf16.argtypes = [vp, vp, i32, i32, i64, i64, vp]
-    l.hs_transpose_bf16_multi.argtypes = [i32, P(vp), P(vp), P(i32), P(i32), P(i64), P(i64), vp]
-    l.hs_dropout.argtypes = [i32, vp, vp, i64, f32, u64, vp]
-    l.hs_relu_fwd.argtypes = [i32, vp, vp, i64, vp]
-    l.hs_relu_bwd.argtypes = [i32, vp, vp, vp, i64, vp]
-    l.hs_gelu_bwd.argtypes = [i32, vp, vp, vp, i64, vp]
-    l.hs_mul_dev_scalar.argtypes = [vp, vp, vp, i64, vp]
-    l.hs_colsum.argtypes = [i32, vp, i64, i32, i32, vp, vp, i64, i32, vp]
-    l.hs_colsum_ws_bytes.argtypes = [i64, i32]
-    l.hs_colsum_ws_bytes.restype = i64
-    l.hs_softmax_fwd.argtypes = [i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u64, vp]
-    l.hs_softmax_bwd.argtypes = [i32, vp, vp, vp, i64, i32, i32, i32, f32, u64, vp]
-    l.hs_bert_embed_fwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, f32, u64, vp]
-    l.hs_bert_embed_bwd.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    l.hs_cross_entropy.argtypes = [vp, vp, vp, f32, i32, i32, vp, vp, vp, vp]
-    l.hs_adam_step_multi.argtypes = [i32, P(vp), P(vp), P(vp), P(vp), P(i64), f32, f32, f32, f32, f32, i32, i32, f32, vp]
-    l.hs_adam_step_multi_shadow.argtypes = [i32, P(vp), P(vp), P(vp), P(vp), P(vp), P(i64), f32, f32, f32, f32, f32, i32, i32, f32, vp]
-    l.hs_weight_shadow_set.argtypes = [vp, vp]
-    l.hs_wgrad_group_begin.argtypes = [vp]
-    l.hs_wgrad_group_end.argtypes = [vp]
-    l.hs_weight_shadow_clear.argtypes = []
-    l.hs_weight_shadow_clear.restype = None
-    l.hs_sgd_step_multi.argtypes = [i32, P(vp), P(vp), P(vp), P(i64), f32, f32, f32, i32, i32, f32, vp]
-    l.hs_muon_prepare_multi.argtypes = [i32, i32, P(vp), P(vp), P(vp), P(i32), P(i32), f32, vp, vp]
-    l.hs_muon_orthogonalize.argtypes = [i32, i32, i32, i32, vp, vp, i64, vp]
-    l.hs_muon_ws_bytes.argtypes = [i32, i32, i32, i32]
-    l.hs_muon_ws_bytes.restype = i64
-    l.hs_muon_apply_multi.argtypes = [i32, i32, P(vp), P(vp), P(vp), P(i32), P(i32), P(f32), f32, f32, vp]
-    l.hs_attention_query.argtypes = [P(AttnDesc), P(i64), P(i64)]
-    l.hs_attention_fwd.argtypes = [P(AttnDesc), vp, vp, vp, vp, vp, i64, vp, i64, vp]
-    l.hs_attention_bwd.argtypes = [P(AttnDesc), vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp]
-    l.hs_resblock_query.argtypes = [P(ResblockDesc), P(i64), P(i64)]
-    l.hs_resblock_fwd.argtypes = [P(ResblockDesc), vp, vp, vp, i64, vp, i64, vp]
-    l.hs_resblock_bwd.argtypes = [P(ResblockDesc), vp, vp, vp, vp, vp, i64, vp, i64, vp]
-    l.hs_stem_query.argtypes = [P(StemDesc), P(i64), P(i64)]
-    l.hs_stem_fwd.argtypes = [P(StemDesc), vp, vp, vp, i64, vp, i64, vp]
-    l.hs_stem_bwd.argtypes = [P(StemDesc), vp, vp, vp, i64, vp, i64, vp]
-    l.hs_bert_layer_query.argtypes = [P(BertLayerDesc), P(i64), P(i64)]
-    l.hs_bert_layer_fwd.argtypes = [P(BertLayerDesc), vp, vp, vp, i64, vp, i64, vp]
-    l.hs_bert_layer_bwd.argtypes = [P(BertLayerDesc), vp, vp, vp, vp, i64, vp, i64, vp]
-    l.hs_abi_sizeof.argtypes = [i32]
-    l.hs_abi_sizeof.restype = i64
-    l.hs_resnet_query.argtypes = [P(ResnetDesc), P(ResnetPlan)]
-    l.hs_resnet_fwd.argtypes = [P(ResnetDesc), vp, vp, i64, vp, i64, vp]
-    l.hs_resnet_debug_offsets.argtypes = [P(ResnetDesc), P(i64), i32]
-    l.hs_resnet_bwd.argtypes = [P(ResnetDesc), P(vp), vp, i64, vp, i64, vp]
-    l.hs_bert_query.argtypes = [P(BertDesc), P(i64), P(i64), P(i64)]
-    l.hs_bert_fwd.argtypes = [P(BertDesc), vp, vp, vp, i64, vp, i64, vp]
-    l.hs_bert_bwd.argtypes = [P(BertDesc), vp, vp, vp, vp, i64, vp, i64, vp]
-    l.hs_linear_fwd.argtypes = [i32, vp, i64, i32, P(Linear), vp, vp, i32, i32, i32, vp, vp, i32, f32, u64, vp]
-    l.hs_linear_bwd.argtypes = [i32, vp, i64, i32, P(Linear), vp, vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, i64, vp]
-    l.hs_linear_bwd_ws_bytes.argtypes = [i64, i32, i32, i32]
-    l.hs_linear_bwd_ws_bytes.restype = i64
-    l.hs_prof_dump.argtypes = [C.c_char_p]
-    l.hs_set_overlap.argtypes = [i32]
-    l.hs_kl_rows.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]
-    l.hs_lstm_cell_fwd.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp]
-    l.hs_lstm_cell_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    l.hs_gru_cell_fwd.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, i32, vp]
-    l.hs_gru_cell_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    l.hs_causal_conv1d_fwd.argtypes = [i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    l.hs_causal_conv1d_bwd.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, vp]
-    l.hs_causal_conv1d_ws_bytes.argtypes = [i32, i32]
-    l.hs_causal_conv1d_ws_bytes.restype = i64
-    l.hs_selective_scan_fwd.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32,
-                                        vp]
-    l.hs_selective_scan_bwd.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32,
-                                        vp, vp, i32, vp, i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]
-    l.hs_selective_scan_ws_bytes.argtypes = [i32, i32, i32]
-    l.hs_selective_scan_ws_bytes.restype = i64
-    l.hs_selective_scan_chunk_len.argtypes = []
-    l.hs_selective_scan_chunk_len.restype = i32
-    l.hs_selective_scan_chunk_len_n.argtypes = [i32]
-    l.hs_selective_scan_chunk_len_n.restype = i32
-    l.hs_selective_scan_ws_bytes_n.argtypes = [i32, i32, i32, i32]
-    l.hs_selective_scan_ws_bytes_n.restype = i64
-    l.hs_selective_scan_chunk_len_nogate.argtypes = [i32]
-    l.hs_selective_scan_chunk_len_nogate.restype = i32
-    l.hs_selective_scan_ws_bytes_nogate.argtypes = [i32, i32, i32, i32]
-    l.hs_selective_scan_ws_bytes_nogate.restype = i64
-    l.hs_conv1d_same_silu_fwd.argtypes = [i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    l.hs_conv1d_same_silu_bwd.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, vp]
-    l.hs_conv1d_same_silu_ws_bytes.argtypes = [i32, i32]
-    l.hs_conv1d_same_silu_ws_bytes.restype = i64
-    l.hs_window_partition.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
-    l.hs_window_reverse.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
-    l.hs_conv3x3_fwd.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-    l.hs_conv3x3_dgrad.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-    l.hs_conv3x3_pack_filter.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp]
-    l.hs_conv3x3_unpack_wgrad.argtypes = [vp, vp, i32, i32, i32, vp]
-    l.hs_pack_image_nhwc.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
-    l.hs_unpack_image_nhwc.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, vp]
-    l.hs_bn_gelu_tanh_fwd.argtypes = [i32, vp, vp, vp, vp, i64, i32, i32, vp]
-    l.hs_bn_scale_residual_fwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i64, vp]
-    l.hs_bn_epilogue_bwd.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, i64, vp, i64, vp]
-    l.hs_bn_epilogue_ws_bytes.argtypes = [i64, i32]
-    l.hs_bn_epilogue_ws_bytes.restype = i64
-    l.hs_window_partition_nhwc.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    l.hs_window_reverse_nhwc.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    l.hs_add_token_bias_fwd.argtypes =[i32, vp, vp, vp, i32, i32, i32, vp]
-    l.hs_add_token_bias_bwd.argtypes = [i32, vp, vp, i32, i32, i32, vp]
-    l.hs_token_seq_assemble_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    l.hs_token_seq_assemble_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    l.hs_transpose_batched_f32.argtypes = [vp, vp, i32, i32, i32, vp]
-    l.hs_concat2_t.argtypes = [i32, vp, i32, vp, i32, vp, i64, vp]
-    l.hs_split2_t.argtypes = [i32, vp, vp, i32, vp, i32, i64, vp]
-    l.hs_prof_calibrate.argtypes = [vp, i32, C.POINTER(C.c_float)]
-    l.hs_tta_expand.argtypes = [vp, vp, i64, i32, i32, P(i32), i32, vp]
-    l.hs_group_mean.argtypes = [vp, vp, i32, i64, vp]
-    l.hs_repeat.argtypes = [i32, vp, vp, i64, i32, vp]
-    l.hs_gradcam.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp]
-    l.hs_stage_images_u8.argtypes = [vp, vp, i32, i32, i32, P(f32), P(f32), vp]
-    l.hs_set_overlap.restype = None
-    l.hs_grad_milestones.argtypes = [i32, P(vp), P(vp)]
-    l.hs_pointwise_stat_rows.argtypes = [i64, i32, i32]
-    l.hs_pointwise_stat_rows.restype = i32
-    l.hs_pointwise_fwd.argtypes = [vp, i64, i32, i32, vp, i32, vp, i32, vp, vp]
-    l.hs_measure_build.argtypes = []
-    l.hs_measure_build.restype = i32
-    l.hs_set_wgrad_nt.argtypes = [i32]
-    l.hs_set_wgrad_nt.restype = None
-    l.hs_set_bert_wgrad_chunks.argtypes = [i32]
-    l.hs_set_bert_wgrad_chunks.restype = None
-    l.hs_set_pack_xcd_spread.argtypes = [i32]
-    l.hs_set_pack_xcd_spread.restype = None
-    l.hs_gemm_k_cols_queued.argtypes = []
-    l.hs_gemm_k_cols_queued.restype = i64
-    l.hs_bert_row_map_bytes.argtypes = [i32, i32]
-    l.hs_bert_row_map_bytes.restype = i64
-    l.hs_bert_row_map.argtypes = [vp, i32, i32, vp, vp]
-    l.hs_transpose_bf16_tokens.argtypes = [vp, vp, i32, i32, i64, i64, vp, vp, vp, vp]
-    l.hs_bert_pack_rows_available.argtypes = []
-    l.hs_bert_pack_rows_available.restype = i32
-    l.hs_dwconv_ws_bytes.argtypes = [i32] * 5
-    l.hs_dwconv_ws_bytes.restype = i64
-    l.hs_dwconv_fwd.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp]
-    l.hs_dwconv_bwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp]
-    l.hs_layerscale_fwd.argtypes = [i32, vp, vp, vp, i32, vp, vp, i64, i32, vp]
-    l.hs_layerscale_bwd.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp, vp, i64, i64, i32, vp]
-    l.hs_layerscale_ws_bytes.argtypes = [i64, i32]
-    l.hs_layerscale_ws_bytes.restype = i64
-    l.hs_patchify_fwd.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    l.hs_patchify_bwd.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-
-
-ABI_STRUCTS = None
-
-
-def abi_structs():
-    """(number for hs_abi_sizeof, ctypes mirror) of every struct of the C ABI"""
-    return [(0, ConvGeom), (1, GemmParams), (2, BnParams), (3, BnBwdParams), (4, AttnDesc), (5, ConvBn), (6, ResblockDesc),
-            (7, StemDesc), (8, Linear), (9, Norm), (10, BertLayerDesc), (11, ResnetDesc), (12, ResnetPlan), (13, BertDesc)]
 
 
 def check(status, what=""):
     if status != HS_OK:
         msg = lib().hs_last_error().decode("utf-8", "replace")
         raise HamspineError(f"{what} failed (status {status}): {msg}")
-
-
-def exported_symbols():
-    """Names declared in include/hamspine.h (used by the CPU-side ABI test)."""
-    txt = open(HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(hs_[a-z0-9_]+)\s*\(", txt)))

@@ -11,34 +11,6 @@ from torch.autograd import Function
 from . import _lib as L
 from . import raw, rt
 
-i32, i64, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
-_declared = False
-
-
-def _l():
-    global _declared
-    l = L.lib()
-    if not _declared:
-        l.hs_kan_features_fwd.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp]
-        l.hs_kan_features_bwd.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]
-        l.hs_kan_pack_weight.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
-        l.hs_kan_unpack_wgrad.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-        l.hs_moe_gate_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, u64, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        l.hs_moe_dispatch_index.argtypes = [vp, i32, i32, vp, vp, vp]
-        l.hs_rows_gather.argtypes = [vp, vp, vp, i32, i32, vp]
-        l.hs_rows_scatter_add.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp]
-        l.hs_rows_scatter_add_bwd.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp]
-        l.hs_moe_gate_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
-        l.hs_moe_combine_fwd.argtypes = [vp, C.POINTER(vp), vp, i32, i32, i32, vp]
-        l.hs_moe_combine_bwd.argtypes = [vp, C.POINTER(vp), vp, C.POINTER(vp), vp, i32, i32, i32, vp]
-        l.hs_supcon_loss.argtypes = [vp, vp, i32, i32, f32, vp, vp, vp, vp]
-        l.hs_supcon_ws_bytes.argtypes = [i32, i32]
-        l.hs_kan_regularization.argtypes = [vp, i64, i32, f32, f32, vp, vp, vp]
-        l.hs_supcon_ws_bytes.restype = i64
-        l.hs_mul_dev_scalar.argtypes = [vp, vp, vp, i64, vp]
-        _declared = True
-    return l
-
 
 def _f32c(t):
     rt.need_gpu(t)
@@ -61,7 +33,7 @@ class KANLinearFn(Function):
         nb = grid_size + order
         Kc = in_f * (1 + nb)
         dev = x.device
-        lib = _l()
+        lib = L.lib()
         feat = torch.empty((B, Kc), dtype=torch.float32, device=dev)
         wcat = torch.empty((out_f, Kc), dtype=torch.float32, device=dev)
         L.check(lib.hs_kan_features_fwd(rt.p(x), rt.p(grid), rt.p(feat), B, in_f, grid_size, order, act, rt.stream()),
@@ -84,7 +56,7 @@ class KANLinearFn(Function):
         nb = grid_size + order
         Kc = in_f * (1 + nb)
         dev = x.device
-        lib = _l()
+        lib = L.lib()
         need_w = any(ctx.needs_input_grad[2:5])
         d_base = d_spline = d_scaler = None
         if need_w:
@@ -125,7 +97,7 @@ class MoEGateFn(Function):
         B, in_f = x.shape
         E = w_gate.shape[1]
         dev = x.device
-        lib = _l()
+        lib = L.lib()
         clean = torch.empty((B, E), dtype=torch.float32, device=dev)
         raw.gemm(x, w_gate, clean, B, E, in_f, a_kind=L.A_KC, b_kind=L.B_RC, lda=in_f, ldb=E)
         rawn = None
@@ -156,7 +128,7 @@ class MoEGateFn(Function):
         B, in_f = x.shape
         E = w_gate.shape[1]
         dev = x.device
-        lib = _l()
+        lib = L.lib()
         dgates = _f32c(dgates) if dgates is not None else torch.zeros((B, E), dtype=torch.float32, device=dev)
         gl = dloss.contiguous().float() if dloss is not None else None
         d_clean = torch.empty((B, E), dtype=torch.float32, device=dev)
@@ -188,7 +160,7 @@ def moe_dispatch_index(gates):
     B, E = gates.shape
     idx = torch.empty((E, B), dtype=torch.int32, device=gates.device)
     cnt = torch.empty(E, dtype=torch.int32, device=gates.device)
-    L.check(_l().hs_moe_dispatch_index(rt.p(gates), B, E, rt.p(idx), rt.p(cnt), rt.stream()), "hs_moe_dispatch_index")
+    L.check(L.lib().hs_moe_dispatch_index(rt.p(gates), B, E, rt.p(idx), rt.p(cnt), rt.stream()), "hs_moe_dispatch_index")
     return idx, cnt.tolist()
 
 
@@ -199,7 +171,7 @@ class RowsGatherFn(Function):
     def forward(ctx, x, idx, n):
         x = _f32c(x)
         out = torch.empty((n, x.shape[1]), dtype=torch.float32, device=x.device)
-        L.check(_l().hs_rows_gather(rt.p(x), rt.p(idx), rt.p(out), n, x.shape[1], rt.stream()), "hs_rows_gather")
+        L.check(L.lib().hs_rows_gather(rt.p(x), rt.p(idx), rt.p(out), n, x.shape[1], rt.stream()), "hs_rows_gather")
         ctx.save_for_backward(idx)
         ctx.meta = (x.shape[0], n)
         return out
@@ -210,7 +182,7 @@ class RowsGatherFn(Function):
         B, n = ctx.meta
         dout = _f32c(dout)
         dx = torch.zeros((B, dout.shape[1]), dtype=torch.float32, device=dout.device)
-        L.check(_l().hs_rows_scatter_add(rt.p(dx), rt.p(idx), None, 0, 0, rt.p(dout), n, dout.shape[1], rt.stream()),
+        L.check(L.lib().hs_rows_scatter_add(rt.p(dx), rt.p(idx), None, 0, 0, rt.p(dout), n, dout.shape[1], rt.stream()),
                 "hs_rows_scatter_add")
         return dx, None, None
 
@@ -230,7 +202,7 @@ class MoESparseCombineFn(Function):
                 O = o.shape[1]
         y = torch.zeros((B, O), dtype=torch.float32, device=gates.device)
         E = gates.shape[1]
-        lib = _l()
+        lib = L.lib()
         for e, (o, n) in enumerate(zip(outs, counts)):
             if n:
                 L.check(lib.hs_rows_scatter_add(rt.p(y), rt.p(idx[e]), rt.p(gates), E, e, rt.p(o), n, O, rt.stream()),
@@ -247,7 +219,7 @@ class MoESparseCombineFn(Function):
         E = gates.shape[1]
         dgates = torch.zeros_like(gates)
         douts = []
-        lib = _l()
+        lib = L.lib()
         for e, (o, n) in enumerate(zip(outs, counts)):
             d = torch.empty_like(o)
             if n:
@@ -267,8 +239,8 @@ class MoECombineFn(Function):
         B, E = gates.shape
         O = outs[0].shape[1]
         y = torch.empty((B, O), dtype=torch.float32, device=gates.device)
-        ptrs = (vp * E)(*[o.data_ptr() for o in outs])
-        L.check(_l().hs_moe_combine_fwd(rt.p(gates), ptrs, rt.p(y), B, E, O, rt.stream()), "hs_moe_combine_fwd")
+        ptrs = (C.c_void_p * E)(*[o.data_ptr() for o in outs])
+        L.check(L.lib().hs_moe_combine_fwd(rt.p(gates), ptrs, rt.p(y), B, E, O, rt.stream()), "hs_moe_combine_fwd")
         ctx.save_for_backward(gates, *outs)
         return y
 
@@ -280,9 +252,9 @@ class MoECombineFn(Function):
         O = outs[0].shape[1]
         douts = [torch.empty_like(o) for o in outs]
         dgates = torch.empty_like(gates)
-        ptrs = (vp * E)(*[o.data_ptr() for o in outs])
-        dptrs = (vp * E)(*[o.data_ptr() for o in douts])
-        L.check(_l().hs_moe_combine_bwd(rt.p(gates), ptrs, rt.p(dy), dptrs, rt.p(dgates), B, E, O, rt.stream()),
+        ptrs = (C.c_void_p * E)(*[o.data_ptr() for o in outs])
+        dptrs = (C.c_void_p * E)(*[o.data_ptr() for o in douts])
+        L.check(L.lib().hs_moe_combine_bwd(rt.p(gates), ptrs, rt.p(dy), dptrs, rt.p(dgates), B, E, O, rt.stream()),
                 "hs_moe_combine_bwd")
         return (dgates, *douts)
 
@@ -293,7 +265,7 @@ class SupConFn(Function):
         feat = _f32c(feat)
         labels = labels.contiguous().long()
         B, D = feat.shape
-        lib = _l()
+        lib = L.lib()
         ws = torch.empty(lib.hs_supcon_ws_bytes(B, D) // 4, dtype=torch.float32, device=feat.device)
         loss = torch.empty((), dtype=torch.float32, device=feat.device)
         df = torch.empty_like(feat)
@@ -307,7 +279,7 @@ class SupConFn(Function):
         (df,) = ctx.saved_tensors
         g = g.contiguous().float()
         out = torch.empty_like(df)
-        L.check(_l().hs_mul_dev_scalar(rt.p(df), rt.p(g), rt.p(out), df.numel(), rt.stream()), "hs_mul_dev_scalar")
+        L.check(L.lib().hs_mul_dev_scalar(rt.p(df), rt.p(g), rt.p(out), df.numel(), rt.stream()), "hs_mul_dev_scalar")
         return out, None, None
 
 
@@ -323,7 +295,7 @@ class KANRegularizationFn(Function):
         rt.need_gpu(w)
         w = w.contiguous()
         loss = torch.empty((), dtype=torch.float32, device=w.device)
-        L.check(_l().hs_kan_regularization(rt.p(w), w.numel() // w.shape[-1], w.shape[-1], ra, re, rt.p(loss), None, rt.stream()),
+        L.check(L.lib().hs_kan_regularization(rt.p(w), w.numel() // w.shape[-1], w.shape[-1], ra, re, rt.p(loss), None, rt.stream()),
                 "hs_kan_regularization")
         ctx.save_for_backward(w)
         ctx.meta = (ra, re)
@@ -334,11 +306,11 @@ class KANRegularizationFn(Function):
         (w,) = ctx.saved_tensors
         ra, re = ctx.meta
         dw = torch.empty_like(w)
-        L.check(_l().hs_kan_regularization(rt.p(w), w.numel() // w.shape[-1], w.shape[-1], ra, re, None, rt.p(dw), rt.stream()),
+        L.check(L.lib().hs_kan_regularization(rt.p(w), w.numel() // w.shape[-1], w.shape[-1], ra, re, None, rt.p(dw), rt.stream()),
                 "hs_kan_regularization")
         g = g.contiguous().float()
         out = torch.empty_like(dw)
-        L.check(_l().hs_mul_dev_scalar(rt.p(dw), rt.p(g), rt.p(out), dw.numel(), rt.stream()), "hs_mul_dev_scalar")
+        L.check(L.lib().hs_mul_dev_scalar(rt.p(dw), rt.p(g), rt.p(out), dw.numel(), rt.stream()), "hs_mul_dev_scalar")
         return out, None, None
 
 

@@ -2,39 +2,11 @@
 sigmoid, softmax entropy, MP-Loss, focal loss, centre-crop resize.  All tensors here are f32 and of
 size O(batch x hidden); each node is one kernel launch per direction.
 """
-import ctypes as C
-
 import torch
 from torch.autograd import Function
 
 from . import _lib as L
 from . import rt
-
-i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
-_declared = False
-
-
-def _l():
-    global _declared
-    l = L.lib()
-    if not _declared:
-        l.hs_select_token_fwd.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp]
-        l.hs_select_token_bwd.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp]
-        l.hs_concat2.argtypes = [vp, i32, vp, i32, vp, i64, vp]
-        l.hs_split2.argtypes = [vp, vp, i32, vp, i32, i64, vp]
-        l.hs_mul.argtypes = [vp, vp, vp, i64, i32, i32, vp]
-        l.hs_rowdot.argtypes = [vp, vp, vp, i32, i32, vp]
-        l.hs_dot.argtypes = [vp, vp, vp, i64, vp]
-        l.hs_sigmoid_fwd.argtypes = [vp, vp, i64, vp]
-        l.hs_sigmoid_bwd.argtypes = [vp, vp, vp, i64, vp]
-        l.hs_softmax_entropy.argtypes = [vp, vp, vp, vp, i32, i32, vp]
-        l.hs_mp_loss.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
-        l.hs_focal_loss.argtypes = [vp, vp, vp, f32, i32, i32, vp, vp, vp]
-        l.hs_center_crop_resize.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-        l.hs_gelu_bwd.argtypes = [i32, vp, vp, vp, i64, vp]
-        l.hs_mul_dev_scalar.argtypes = [vp, vp, vp, i64, vp]
-        _declared = True
-    return l
 
 
 def _f32c(t):
@@ -53,7 +25,7 @@ class SelectTokenFn(Function):
         x = x.contiguous()
         B, Nt, H = x.shape
         o = torch.empty((B, H), dtype=torch.float32, device=x.device)
-        L.check(_l().hs_select_token_fwd(rt.hs_dtype(x), rt.p(x), rt.p(o), B, Nt, H, t, rt.stream()), "hs_select_token_fwd")
+        L.check(L.lib().hs_select_token_fwd(rt.hs_dtype(x), rt.p(x), rt.p(o), B, Nt, H, t, rt.stream()), "hs_select_token_fwd")
         ctx.meta = (x.shape, x.dtype, t)
         return o
 
@@ -62,7 +34,7 @@ class SelectTokenFn(Function):
         (B, Nt, H), dt, t = ctx.meta
         g = _f32c(g)
         dx = torch.empty((B, Nt, H), dtype=dt, device=g.device)
-        L.check(_l().hs_select_token_bwd(rt.hs_dtype(dt), rt.p(g), rt.p(dx), B, Nt, H, t, rt.stream()), "hs_select_token_bwd")
+        L.check(L.lib().hs_select_token_bwd(rt.hs_dtype(dt), rt.p(g), rt.p(dx), B, Nt, H, t, rt.stream()), "hs_select_token_bwd")
         return dx, None
 
 
@@ -73,7 +45,7 @@ class Concat2Fn(Function):
         rows = a.numel() // a.shape[-1]
         Ha, Hb = a.shape[-1], b.shape[-1]
         o = torch.empty(a.shape[:-1] + (Ha + Hb,), dtype=torch.float32, device=a.device)
-        L.check(_l().hs_concat2(rt.p(a), Ha, rt.p(b), Hb, rt.p(o), rows, rt.stream()), "hs_concat2")
+        L.check(L.lib().hs_concat2(rt.p(a), Ha, rt.p(b), Hb, rt.p(o), rows, rt.stream()), "hs_concat2")
         ctx.meta = (a.shape, b.shape)
         return o
 
@@ -84,13 +56,13 @@ class Concat2Fn(Function):
         da = torch.empty(sa, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
         db = torch.empty(sb, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[1] else None
         rows = g.numel() // g.shape[-1]
-        L.check(_l().hs_split2(rt.p(g), rt.p(da), sa[-1], rt.p(db), sb[-1], rows, rt.stream()), "hs_split2")
+        L.check(L.lib().hs_split2(rt.p(g), rt.p(da), sa[-1], rt.p(db), sb[-1], rows, rt.stream()), "hs_split2")
         return da, db
 
 
 def _mul_raw(a, b, mode, rows, cols):
     o = torch.empty_like(a)
-    L.check(_l().hs_mul(rt.p(a), rt.p(b), rt.p(o), rows, cols, mode, rt.stream()), "hs_mul")
+    L.check(L.lib().hs_mul(rt.p(a), rt.p(b), rt.p(o), rows, cols, mode, rt.stream()), "hs_mul")
     return o
 
 
@@ -118,7 +90,7 @@ class ScaleBySigmoidFn(Function):
     def forward(ctx, x, w):
         x, w = _f32c(x), _f32c(w)
         s = torch.empty_like(w)
-        L.check(_l().hs_sigmoid_fwd(rt.p(w), rt.p(s), 1, rt.stream()), "hs_sigmoid_fwd")
+        L.check(L.lib().hs_sigmoid_fwd(rt.p(w), rt.p(s), 1, rt.stream()), "hs_sigmoid_fwd")
         ctx.save_for_backward(x, s)
         return _mul_raw(x, s, 2, x.numel(), 1)
 
@@ -130,9 +102,9 @@ class ScaleBySigmoidFn(Function):
         dw = None
         if ctx.needs_input_grad[1]:
             d = torch.empty_like(s)
-            L.check(_l().hs_dot(rt.p(g), rt.p(x), rt.p(d), g.numel(), rt.stream()), "hs_dot")
+            L.check(L.lib().hs_dot(rt.p(g), rt.p(x), rt.p(d), g.numel(), rt.stream()), "hs_dot")
             dw = torch.empty_like(s)
-            L.check(_l().hs_sigmoid_bwd(rt.p(d), rt.p(s), rt.p(dw), 1, rt.stream()), "hs_sigmoid_bwd")
+            L.check(L.lib().hs_sigmoid_bwd(rt.p(d), rt.p(s), rt.p(dw), 1, rt.stream()), "hs_sigmoid_bwd")
         return dx, dw
 
 
@@ -141,7 +113,7 @@ class SigmoidFn(Function):
     def forward(ctx, x):
         x = _f32c(x)
         y = torch.empty_like(x)
-        L.check(_l().hs_sigmoid_fwd(rt.p(x), rt.p(y), x.numel(), rt.stream()), "hs_sigmoid_fwd")
+        L.check(L.lib().hs_sigmoid_fwd(rt.p(x), rt.p(y), x.numel(), rt.stream()), "hs_sigmoid_fwd")
         ctx.save_for_backward(y)
         return y
 
@@ -150,7 +122,7 @@ class SigmoidFn(Function):
         (y,) = ctx.saved_tensors
         g = _f32c(g)
         dx = torch.empty_like(y)
-        L.check(_l().hs_sigmoid_bwd(rt.p(g), rt.p(y), rt.p(dx), y.numel(), rt.stream()), "hs_sigmoid_bwd")
+        L.check(L.lib().hs_sigmoid_bwd(rt.p(g), rt.p(y), rt.p(dx), y.numel(), rt.stream()), "hs_sigmoid_bwd")
         return dx
 
 
@@ -162,7 +134,7 @@ class EntropyFn(Function):
         z = _f32c(z)
         B, Cn = z.shape
         e = torch.empty((B, 1), dtype=torch.float32, device=z.device)
-        L.check(_l().hs_softmax_entropy(rt.p(z), None, rt.p(e), None, B, Cn, rt.stream()), "hs_softmax_entropy")
+        L.check(L.lib().hs_softmax_entropy(rt.p(z), None, rt.p(e), None, B, Cn, rt.stream()), "hs_softmax_entropy")
         ctx.save_for_backward(z)
         return e
 
@@ -172,7 +144,7 @@ class EntropyFn(Function):
         g = _f32c(g)
         B, Cn = z.shape
         dz = torch.empty_like(z)
-        L.check(_l().hs_softmax_entropy(rt.p(z), rt.p(g), None, rt.p(dz), B, Cn, rt.stream()), "hs_softmax_entropy")
+        L.check(L.lib().hs_softmax_entropy(rt.p(z), rt.p(g), None, rt.p(dz), B, Cn, rt.stream()), "hs_softmax_entropy")
         return dz
 
 
@@ -183,7 +155,7 @@ class GateMixFn(Function):
     def forward(ctx, alpha, ll, lc):
         alpha, ll, lc = _f32c(alpha), _f32c(ll), _f32c(lc)
         B, Cn = ll.shape
-        lib = _l()
+        lib = L.lib()
         # out = lc + alpha*(ll - lc)
         diff = torch.empty_like(ll)
         L.check(lib.hs_axpby(L.HS_F32, L.HS_F32, rt.p(ll), rt.p(lc), rt.p(diff), ll.numel(), 1.0, -1.0, rt.stream()), "hs_axpby")
@@ -198,7 +170,7 @@ class GateMixFn(Function):
         alpha, diff = ctx.saved_tensors
         g = _f32c(g)
         B, Cn = g.shape
-        lib = _l()
+        lib = L.lib()
         dalpha = torch.empty_like(alpha)
         L.check(lib.hs_rowdot(rt.p(g), rt.p(diff), rt.p(dalpha), B, Cn, rt.stream()), "hs_rowdot")
         dll = _mul_raw(g, alpha, 1, B, Cn)
@@ -216,7 +188,7 @@ class _LossWithGrads(Function):
         outs = []
         for d in grads:
             o = torch.empty_like(d)
-            L.check(_l().hs_mul_dev_scalar(rt.p(d), rt.p(g), rt.p(o), d.numel(), rt.stream()), "hs_mul_dev_scalar")
+            L.check(L.lib().hs_mul_dev_scalar(rt.p(d), rt.p(g), rt.p(o), d.numel(), rt.stream()), "hs_mul_dev_scalar")
             outs.append(o)
         return outs
 
@@ -230,7 +202,7 @@ class MPLossFn(_LossWithGrads):
         loss = torch.empty((), dtype=torch.float32, device=zi.device)
         di, dt_, df = torch.empty_like(zi), torch.empty_like(zt), torch.empty_like(zf)
         scratch = torch.empty(B, dtype=torch.float32, device=zi.device)
-        L.check(_l().hs_mp_loss(rt.p(zi), rt.p(zt), rt.p(zf), rt.p(labels), B, Cn, rt.p(loss), rt.p(di), rt.p(dt_), rt.p(df),
+        L.check(L.lib().hs_mp_loss(rt.p(zi), rt.p(zt), rt.p(zf), rt.p(labels), B, Cn, rt.p(loss), rt.p(di), rt.p(dt_), rt.p(df),
                                 rt.p(scratch), rt.stream()), "hs_mp_loss")
         ctx.save_for_backward(di, dt_, df)
         return loss
@@ -249,7 +221,7 @@ class FocalLossFn(_LossWithGrads):
         B, Cn = z.shape
         loss = torch.empty((), dtype=torch.float32, device=z.device)
         dz = torch.empty_like(z)
-        L.check(_l().hs_focal_loss(rt.p(z), rt.p(labels), rt.p(weight), gamma, B, Cn, rt.p(loss), rt.p(dz), rt.stream()),
+        L.check(L.lib().hs_focal_loss(rt.p(z), rt.p(labels), rt.p(weight), gamma, B, Cn, rt.p(loss), rt.p(dz), rt.stream()),
                 "hs_focal_loss")
         ctx.save_for_backward(dz)
         return loss
@@ -269,7 +241,7 @@ class KLRowsFn(Function):
         cols = p.shape[-1]
         rows = p.numel() // cols
         o = torch.empty(p.shape[:-1], dtype=torch.float32, device=p.device)
-        L.check(_l().hs_kl_rows(rt.p(p), rt.p(q), rt.p(o), None, None, None, rows, cols, eps, rt.stream()), "hs_kl_rows")
+        L.check(L.lib().hs_kl_rows(rt.p(p), rt.p(q), rt.p(o), None, None, None, rows, cols, eps, rt.stream()), "hs_kl_rows")
         ctx.save_for_backward(p, q)
         ctx.eps = eps
         return o
@@ -282,7 +254,7 @@ class KLRowsFn(Function):
         g = _f32c(g)
         dp = torch.empty_like(p) if ctx.needs_input_grad[0] else None
         dq = torch.empty_like(q) if ctx.needs_input_grad[1] else None
-        L.check(_l().hs_kl_rows(rt.p(p), rt.p(q), None, rt.p(g), rt.p(dp), rt.p(dq), rows, cols, ctx.eps, rt.stream()),
+        L.check(L.lib().hs_kl_rows(rt.p(p), rt.p(q), None, rt.p(g), rt.p(dp), rt.p(dq), rows, cols, ctx.eps, rt.stream()),
                 "hs_kl_rows")
         return dp, dq, None
 
@@ -307,7 +279,7 @@ class ConcatTokensFn(Function):
         rows = a.numel() // a.shape[-1]
         Ha, Hb = a.shape[-1], b.shape[-1]
         o = torch.empty(a.shape[:-1] + (Ha + Hb,), dtype=a.dtype, device=a.device)
-        L.check(_l().hs_concat2_t(rt.hs_dtype(a), rt.p(a), Ha, rt.p(b), Hb, rt.p(o), rows, rt.stream()), "hs_concat2_t")
+        L.check(L.lib().hs_concat2_t(rt.hs_dtype(a), rt.p(a), Ha, rt.p(b), Hb, rt.p(o), rows, rt.stream()), "hs_concat2_t")
         ctx.meta = (a.shape, b.shape, a.dtype)
         return o
 
@@ -320,7 +292,7 @@ class ConcatTokensFn(Function):
         da = torch.empty(sa, dtype=dt, device=g.device) if ctx.needs_input_grad[0] else None
         db = torch.empty(sb, dtype=dt, device=g.device) if ctx.needs_input_grad[1] else None
         rows = g.numel() // g.shape[-1]
-        L.check(_l().hs_split2_t(rt.hs_dtype(dt), rt.p(g), rt.p(da), sa[-1], rt.p(db), sb[-1], rows, rt.stream()), "hs_split2_t")
+        L.check(L.lib().hs_split2_t(rt.hs_dtype(dt), rt.p(g), rt.p(da), sa[-1], rt.p(db), sb[-1], rows, rt.stream()), "hs_split2_t")
         return da, db
 
 
@@ -370,5 +342,5 @@ def center_crop_resize(x, ratio):
     if (ch, cw) == (H, W):
         return x
     o = torch.empty_like(x)
-    L.check(_l().hs_center_crop_resize(rt.p(x), rt.p(o), N, Cc, H, W, y0, x0, ch, cw, rt.stream()), "hs_center_crop_resize")
+    L.check(L.lib().hs_center_crop_resize(rt.p(x), rt.p(o), N, Cc, H, W, y0, x0, ch, cw, rt.stream()), "hs_center_crop_resize")
     return o

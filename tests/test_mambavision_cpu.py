@@ -135,23 +135,27 @@ def test_refusals_raise_on_the_cpu():
 
 
 def test_header_declares_and_binding_lists_the_new_entry_points():
+    import ctypes
     import hamspine._lib as L
     names = {"hs_conv1d_same_silu_fwd": "hs_status", "hs_conv1d_same_silu_bwd": "hs_status", "hs_conv1d_same_silu_ws_bytes": "int64_t",
              "hs_window_partition": "hs_status", "hs_window_reverse": "hs_status", "hs_selective_scan_chunk_len_nogate": "int32_t",
              "hs_selective_scan_ws_bytes_nogate": "int64_t"}
     syms = L.exported_symbols()
     header = open(L.HEADER_PATH).read()
-    binding = open(os.path.join(os.path.dirname(L.__file__), "_lib.py")).read()
+    lib = L.lib()
+    restypes = {"hs_status": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}
     for n, ret in names.items():
         assert n in syms, n
         assert re.search(ret + r"\s+" + n + r"\s*\(", header), n
-        assert f"l.{n}.argtypes" in binding, n
+        # the binding is derived from the header: as many argument types as the prototype has parameters, and its return type
+        args = re.search(ret + r"\s+" + n + r"\s*\(([^()]*)\)\s*;", header)[1]
+        assert len(getattr(lib, n).argtypes) == (0 if args.strip() == "void" else args.count(",") + 1), n
+        assert getattr(lib, n).restype is restypes[ret], n
     # every new declaration carries the reference lines it replaces
     for n in ("hs_conv1d_same_silu_fwd", "hs_conv1d_same_silu_bwd", "hs_window_partition", "hs_window_reverse",
               "hs_selective_scan_chunk_len_nogate"):
         head = header[:header.index(n + "(")]
         assert "ConNexT/models/block/mamba_vision.py:" in head[head.rindex("/*"):], n
-    lib = L.lib()
     for n in names:
         assert hasattr(lib, n) and getattr(lib, n).argtypes is not None, n
     # host logic only: 8 states without a gate save a state every 16 steps and reduce over blocks of 32 channels

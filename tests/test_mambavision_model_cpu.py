@@ -206,6 +206,7 @@ def test_non_strict_loading_reports_instead_of_raising(tmp_path, capsys):
 
 
 def test_header_declares_and_binding_lists_the_new_entry_points():
+    import ctypes
     import hamspine._lib as L
     names = {"hs_conv3x3_fwd": "hs_status", "hs_conv3x3_dgrad": "hs_status", "hs_conv3x3_pack_filter": "hs_status",
              "hs_conv3x3_unpack_wgrad": "hs_status", "hs_pack_image_nhwc": "hs_status", "hs_unpack_image_nhwc": "hs_status",
@@ -213,14 +214,17 @@ def test_header_declares_and_binding_lists_the_new_entry_points():
              "hs_bn_epilogue_ws_bytes": "int64_t", "hs_window_partition_nhwc": "hs_status", "hs_window_reverse_nhwc": "hs_status"}
     syms = L.exported_symbols()
     header = open(L.HEADER_PATH).read()
-    binding = open(os.path.join(os.path.dirname(L.__file__), "_lib.py")).read()
+    lib = L.lib()
+    restypes = {"hs_status": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}
     for n, ret in names.items():
         assert n in syms, n
         assert re.search(ret + r"\s+" + n + r"\s*\(", header), n
-        assert f"l.{n}.argtypes" in binding, n
+        # the binding is derived from the header: as many argument types as the prototype has parameters, and its return type
+        args = re.search(ret + r"\s+" + n + r"\s*\(([^()]*)\)\s*;", header)[1]
+        assert len(getattr(lib, n).argtypes) == (0 if args.strip() == "void" else args.count(",") + 1), n
+        assert getattr(lib, n).restype is restypes[ret], n
         head = header[:header.index(n + "(")]          # every new declaration carries the reference lines it replaces
         assert "ConNexT/models/block/mamba_vision.py:" in head[head.rindex("/*"):], n
-    lib = L.lib()
     for n in names:
         assert hasattr(lib, n) and getattr(lib, n).argtypes is not None, n
     # host logic only: row blocks of at least 64 rows, at most 256 of them, two sums per channel and three coefficients

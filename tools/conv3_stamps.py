@@ -1,6 +1,5 @@
 """Per-workgroup timeline of the 3x3 halo-patch kernel (csrc/conv3.hip) from in-kernel clock stamps, ResNet50 shapes at batch 32.
 python tools/conv3_stamps.py [plain]"""
-import ctypes as C
 import os
 import sys
 
@@ -18,7 +17,6 @@ SHAPES = [(32, 64, 56, 56, 64), (32, 128, 28, 28, 128), (32, 256, 14, 14, 256), 
 def main():
     plain = len(sys.argv) > 1 and sys.argv[1] == "plain"
     lib = L.lib()
-    lib.hs_gemm_debug_stamps.argtypes = [C.c_void_p]
     for Nb, Cc, H, W, K in SHAPES:
         x = (torch.randn(Nb, Cc, H, W, device=DEV) * 0.5).to(BF).contiguous(memory_format=torch.channels_last)
         w = (torch.randn(K, Cc, 3, 3, device=DEV) * 0.1).to(BF).contiguous(memory_format=torch.channels_last)

@@ -13,13 +13,10 @@ from hamspine import _lib as L  # noqa: E402
 from hamspine import raw  # noqa: E402
 
 lib = L.lib()
-lib.hs_gemm_debug.argtypes = [C.c_int32, C.c_int32]
 DEV = "cuda"
 BF = torch.bfloat16
 
 
-lib.hs_prof_enable.argtypes = [C.c_int32]
-lib.hs_prof_collect.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
 
 
 FLUSH = None

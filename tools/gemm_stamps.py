@@ -1,7 +1,6 @@
 """Per-workgroup timeline of one bf16 GEMM launch from in-kernel shader-clock stamps (hs_gemm_debug_stamps):
 where a tile's time goes -- set-up, first DMA latency, K loop, epilogue -- and how the workgroups' starts spread.
 usage: gemm_stamps.py kind M N K [cfg]     (run on the GPU box)"""
-import ctypes as C
 import os
 import sys
 
@@ -16,7 +15,6 @@ def main():
     cfg = int(sys.argv[5]) if len(sys.argv) > 5 else -1
     bits = int(sys.argv[6]) if len(sys.argv) > 6 else 0
     lib = gb.lib
-    lib.hs_gemm_debug_stamps.argtypes = [C.c_void_p]
     lib.hs_gemm_debug(cfg, bits)
     fn = gb.gemm_case(kind, M, N, K)
     for _ in range(3):

@@ -13,9 +13,6 @@ from hamspine import _lib as L  # noqa: E402
 from hamspine import raw  # noqa: E402
 
 lib = L.lib()
-lib.hs_gemm_debug.argtypes = [C.c_int32, C.c_int32]
-lib.hs_prof_enable.argtypes = [C.c_int32]
-lib.hs_prof_collect.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
 DEV, BF = "cuda", torch.bfloat16
 CFGS = {-1: "auto", 1: "128x64", 2: "64x64", 5: "128x128k32", 4: "256x128", 7: "p8-256", 8: "p8-256x128", 9: "p8-128"}
 COLD = "--cold" in sys.argv

@@ -2,7 +2,6 @@
 microseconds per 64-deep K tile (slope) and the per-launch ramp (intercept); the vendor
 library (torch.mm -> hipBLASLt) on the same operands as a mark.  Warm operands, random data, interleaved rounds.
    python tools/p8_slope.py"""
-import ctypes as C
 import os
 import sys
 
@@ -14,7 +13,6 @@ from hamspine import _lib as L  # noqa: E402
 from hamspine import raw  # noqa: E402
 
 lib = L.lib()
-lib.hs_gemm_debug.argtypes = [C.c_int32, C.c_int32]
 DEV, BF = "cuda", torch.bfloat16
 
 

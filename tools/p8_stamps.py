@@ -1,7 +1,6 @@
 """Where one K tile of the pipelined GEMM body spends its cycles: shader-clock stamps around every segment of the middle K
 tile, waves 0 (early group) and 4 (late group) of every workgroup (diagnostic kernel build, hs_gemm_debug_stamps).
    python tools/p8_stamps.py M N K [ablate]"""
-import ctypes as C
 import os
 import sys
 
@@ -13,8 +12,6 @@ from hamspine import _lib as L  # noqa: E402
 from hamspine import raw  # noqa: E402
 
 lib = L.lib()
-lib.hs_gemm_debug.argtypes = [C.c_int32, C.c_int32]
-lib.hs_gemm_debug_stamps.argtypes = [C.c_void_p]
 DEV, BF = "cuda", torch.bfloat16
 NAMES = ["p0 reads issued+returned", "p0 dma+vmcnt+barrier", "p0 16 MFMA issued", "p0 barrier",
          "p1 reads", "p1 dma+vmcnt+barrier", "p1 MFMA", "p1 barrier",
