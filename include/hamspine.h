@@ -373,7 +373,9 @@ hs_status hs_bert_embed_fwd(int32_t dtype, const int64_t* ids, const float* word
 hs_status hs_bert_embed_bwd(int32_t dtype, const int64_t* ids, const void* dsum, float* dword, float* dpos, int32_t B,
                             int32_t L, int32_t H, int32_t V, int32_t pad_id, void* stream);
 /* mean-reduced CrossEntropyLoss(weight, label_smoothing): writes the scalar loss, d loss / d logits
-   (optional) and the per-row unreduced losses (optional). reference scripts/train.py:240,252-254. */
+   (optional) and the per-row unreduced losses (optional). reference scripts/train.py:240,252-254.
+   Precondition, here and in hs_mp_loss / hs_focal_loss: every label lies in [0, C).  Labels are not checked (there is no
+   ignore_index); one outside the range reads logits and weight out of bounds. */
 hs_status hs_cross_entropy(const float* logits, const int64_t* labels, const float* weight, float label_smoothing,
                            int32_t B, int32_t C, float* loss, float* dlogits, float* row_loss, void* stream);
 /* fused multi-tensor Adam (decoupled=0) / AdamW (decoupled=1) step over f32 tensors. */
@@ -458,7 +460,8 @@ hs_status hs_split2_t(int32_t dtype, const void* g, void* da, int32_t Ha, void* 
 hs_status hs_mul(const float* a, const float* b, float* out, int64_t rows, int32_t cols, int32_t b_mode, void* stream);
 hs_status hs_rowdot(const float* a, const float* b, float* out, int32_t rows, int32_t cols, void* stream);
 /* out[r] = KL(p[r] || q[r]) on probabilities clamped to [eps, 1] (reference mibf_net/attention.py:25-28).  With w (the
-   incoming gradient per row) dp / dq receive the gradients; out may then be NULL. */
+   incoming gradient per row) dp / dq receive the gradients; out may then be NULL.  As with torch.clamp, an entry exactly on
+   a bound (p == eps, p == 1) passes its gradient; one outside [eps, 1] gets 0. */
 hs_status hs_kl_rows(const float* p, const float* q, float* out, const float* w, float* dp, float* dq, int32_t rows,
                      int32_t cols, float eps, void* stream);
 /* out[0] = sum a[i]*b[i] (b NULL: sum a). */
@@ -474,7 +477,10 @@ hs_status hs_softmax_entropy(const float* logits, const float* g, float* ent, fl
 hs_status hs_mp_loss(const float* image_logits, const float* text_logits, const float* fused_logits, const int64_t* labels,
                      int32_t B, int32_t C, float* loss, float* d_image, float* d_text, float* d_fused, float* scratch,
                      void* stream);
-/* FocalLoss(gamma, weight), mean reduction (reference scripts/train.py:46-61). */
+/* FocalLoss(gamma, weight), mean reduction (reference scripts/train.py:46-61).  gamma = 0 is plain CE with the plain mean
+   over the batch.  On a saturated row (ce == 0 in float32: the label class leads by about 17 or more) the gradient is 0 for
+   gamma = 0 and for gamma >= 1; for 0 < gamma < 1 it is NaN, as in the reference, whose (1 - pt)^(gamma - 1) is infinite
+   there. */
 hs_status hs_focal_loss(const float* logits, const int64_t* labels, const float* weight, float gamma, int32_t B, int32_t C,
                         float* loss, float* dlogits, void* stream);
 /* out = bilinear_resize(x[:, :, y0:y0+ch, x0:x0+cw], (H, W)), align_corners=False, f32 NCHW
@@ -657,7 +663,10 @@ hs_status hs_kan_regularization(const float* w, int64_t rows, int32_t coeffs, fl
                                 float* loss, float* dw, void* stream);
 
 /* SupConLoss(temperature) on (B, D) features, mean over anchors, loss + d/d features
-   (reference scripts/train.py:23-44).  ws: hs_supcon_ws_bytes(B, D). */
+   (reference scripts/train.py:23-44).  ws: hs_supcon_ws_bytes(B, D); its size is not checked.  Single workgroup:
+   1 <= B <= 256 is required, a larger batch is refused before anything is written.  An anchor without positives adds
+   exactly 0 to the loss and to the gradient.  A zero-norm row is normalised as F.normalize does, by max(norm, 1e-12): its
+   feature stays 0, and its gradient is the gradient of the normalised feature times 1e12. */
 hs_status hs_supcon_loss(const float* feat, const int64_t* labels, int32_t B, int32_t D, float temperature, float* loss,
                          float* dfeat, float* ws, void* stream);
 int64_t hs_supcon_ws_bytes(int32_t B, int32_t D);
@@ -700,7 +709,9 @@ hs_status hs_patchify_bwd(int32_t dtype, const void* dpatch, void* dx, int32_t N
 /* feat[b] = [act(x[b,:]) | bases(x[b,0]) .. bases(x[b,in-1])], row length in*(1 + grid_size + order);
    grid: (in, grid_size + 2*order + 1) knots.  base_act = the layer's `base_activation` (kan1.py:17,35): 0 SiLU (the
    reference default), 1 GELU (erf), 2 ReLU, 3 identity -- the KAN classifier head (reference modules/heads.py:108-140,
-   `act_mode`) selects it. */
+   `act_mode`) selects it.  At most 32 knots per feature (grid_size + 2*order + 1 <= 32), more are refused.  The knots of a
+   feature must increase strictly.  A basis is 1 on [g[j], g[j+1]): x on a knot belongs to the interval it opens, and x at or
+   beyond the last knot, or below the first, has all bases (and their derivatives) 0. */
 hs_status hs_kan_features_fwd(const float* x, const float* grid, float* feat, int64_t B, int32_t in_f, int32_t grid_size,
                               int32_t order, int32_t base_act, void* stream);
 hs_status hs_kan_features_bwd(const float* x, const float* grid, const float* dfeat, float* dx, int64_t B, int32_t in_f,

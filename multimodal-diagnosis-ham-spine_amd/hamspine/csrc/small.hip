@@ -82,7 +82,8 @@ __global__ void rowdot_kernel(const float* __restrict__ a, const float* __restri
     if (lane == 0) o[r] = acc;
 }
 // KL(p || q) per row on probabilities clamped to [eps, 1] (reference mibf_net/attention.py:25-28); one wave per row.
-// dp / dq (optional): gradients of sum_r w[r] * kl[r]; the clamp passes no gradient where it is active.
+// dp / dq (optional): gradients of sum_r w[r] * kl[r]; the clamp passes no gradient where it is active, and passes it on
+// both bounds (p == eps, p == 1: a float32 softmax with a margin of 17 is exactly 1), as torch.clamp does.
 __global__ void kl_rows_kernel(const float* __restrict__ p, const float* __restrict__ q, float* __restrict__ o,
                                const float* __restrict__ w, float* __restrict__ dp, float* __restrict__ dq, int rows,
                                int cols, float eps) {
@@ -97,8 +98,8 @@ __global__ void kl_rows_kernel(const float* __restrict__ p, const float* __restr
         const float pc = fminf(fmaxf(pr, eps), 1.f), qc = fminf(fmaxf(qr, eps), 1.f);
         const float lp = __logf(pc), lq = __logf(qc);
         acc += pc * (lp - lq);
-        if (dp) dp[i] = (pr > eps && pr < 1.f) ? wr * (lp - lq + 1.f) : 0.f;
-        if (dq) dq[i] = (qr > eps && qr < 1.f) ? -wr * pc / qc : 0.f;
+        if (dp) dp[i] = (pr >= eps && pr <= 1.f) ? wr * (lp - lq + 1.f) : 0.f;
+        if (dq) dq[i] = (qr >= eps && qr <= 1.f) ? -wr * pc / qc : 0.f;
     }
     acc = wave_sum(acc);
     if (lane == 0 && o) o[r] = acc;
@@ -291,7 +292,9 @@ __global__ __launch_bounds__(256) void focal_kernel(const float* __restrict__ z,
         const float om = 1.f - pt;
         acc += powf(om, gamma) * ce;
         if (dz) {
-            const float dce = (powf(om, gamma) + gamma * powf(om, gamma - 1.f) * pt * ce) / (float)B;
+            // gamma == 0 is plain CE: (1-pt)^0 has no slope, also on a saturated row (om == 0), where 0 * om^-1 is NaN
+            const float slope = gamma == 0.f ? 0.f : gamma * powf(om, gamma - 1.f) * pt * ce;
+            const float dce = (powf(om, gamma) + slope) / (float)B;
             for (int c = 0; c < C; ++c) {
                 const float p = __expf(a[c] - m) / s;
                 dz[(long long)b * C + c] = dce * wy * (p - (c == y ? 1.f : 0.f));
