@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void gather3_kernel(const float* __restrict__ 
     dst[i] = w == 0 ? a[k] : (w == 1 ? b[k] : c[k]);
 }
 
-int gemm_impl(const hs_gemm_params* p, hipStream_t stream);
+int gemm_impl(const hs_gemm_params* p, hipStream_t stream, const ResGather* rg = nullptr);
 int gemm_stat_rows(const hs_gemm_params* p);
 int gemm_bn_finish_rows(const hs_gemm_params* p);
 int gemm_tile_rows(const hs_gemm_params* p);
@@ -283,7 +283,8 @@ static hs_gemm_params gemm_defaults(int dt) {
     return p;
 }
 // wgrad-style GEMMs reduce over a long K into a small output: pick split-K, borrow slabs from ws.
-static int gemm_splitk(Run& r, hs_gemm_params& p, bool may_defer = false) {
+// rg (optional): the residual is compact (ResGather); never with may_defer
+static int gemm_splitk(Run& r, hs_gemm_params& p, bool may_defer = false, const ResGather* rg = nullptr) {
     const int split = hs_gemm_suggest_split(p.M, p.N, p.K, p.dtype);
     const long long mk = r.ws.mark();
     p.split_k = split;
@@ -296,7 +297,7 @@ static int gemm_splitk(Run& r, hs_gemm_params& p, bool may_defer = false) {
         }
         if (may_defer && (knock() & 1)) {
         } else if (defer) HS_PROPAGATE(gemm_group_add(p.b_kind == HS_B_CONV ? r.grp_conv : r.grp_pw, &p, r.s));
-        else HS_PROPAGATE(gemm_impl(&p, r.s));
+        else HS_PROPAGATE(gemm_impl(&p, r.s, rg));
     }
     if (defer) return HS_OK;                 // the slabs stay allocated until the grouped launch has run
     // with a side stream, slabs of consecutive GEMMs may be live concurrently: keep them until the composite ends
@@ -754,6 +755,16 @@ static hs_conv_geom geom_of(const ConvShape& s) {
     return g;
 }
 static bool is_pointwise(const ConvShape& s) { return s.R == 1 && s.stride == 1 && s.pad == 0; }
+// A 1x1 pad-0 stride-2 convolution (the downsample branch of a strided block) reads only the even pixels: its data gradient is
+// the plain GEMM dy[N*P*Q][Cout] . W[Cout][Cin], and every other row of the full-size gradient is a structural zero.  bf16 mode
+// writes just that -- a COMPACT gradient [N][P][Q][Cin] -- and the block's stage-0 data gradient gathers it as its residual
+// (ResGather).  HAMSPINE_DS_COMPACT=0 keeps the full-size parity-ordered route; read per call, so tests and A/B runs compare
+// both settings in one process.  The exact-f32 mode always takes the full-size route.
+static bool ds_compact(int dt, const ConvShape& s) {
+    if (dt != HS_BF16 || s.R != 1 || s.stride != 2 || s.pad != 0) return false;
+    const char* e = getenv("HAMSPINE_DS_COMPACT");
+    return !(e && e[0] == '0');
+}
 static bool fused_ln_bwd_enabled() {        // HAMSPINE_FUSED_LN_BWD=0: separate LayerNorm-backward / dropout / column-sum passes
     static int v = -1;
     if (v < 0) {
@@ -900,9 +911,24 @@ static bool fused_bn_bwd_enabled() {        // HAMSPINE_FUSED_BN_BWD=0: BatchNor
     }
     return v == 1;
 }
+// compact (with a 1x1 pad-0 stride-2 convolution): dx is the compact gradient [N][P][Q][Cin], one unsplit pointwise GEMM.
+// rg (optional): `residual` is such a compact gradient over this convolution's input grid.
 static int conv_dgrad_run(Run& r, const ConvShape& s, const void* dy, const void* w_c, void* dx, const void* residual,
-                          const BnSums* bnb = nullptr) {
+                          const BnSums* bnb = nullptr, const ResGather* rg = nullptr, bool compact = false) {
     hs_gemm_params p = gemm_defaults(r.dt);
+    if (compact) {
+        p.M = (int)((long long)s.N * s.P * s.Q); p.N = s.Cin; p.K = s.Cout;
+        p.A = dy; p.B = w_c;
+        p.a_elems = (long long)p.M * s.Cout;
+        p.b_elems = (long long)s.Cout * s.Cin;
+        p.a_kind = HS_A_KC; p.lda = s.Cout;
+        p.b_kind = HS_B_RC; p.ldb = s.Cin;
+        p.D = dx; p.ldd = s.Cin;
+        if (!r.plan && (knock() & 512)) return HS_OK;
+        // not gemm_splitk: the full-size launch it replaces is unsplit, and a K split would change the order of the sums
+        CALL(r, gemm_impl(&p, r.s));
+        return HS_OK;
+    }
     p.M = (int)((long long)s.N * s.H * s.W); p.N = s.Cin; p.K = s.R * s.R * s.Cout;
     p.A = dy; p.B = w_c;
     p.a_elems = (long long)s.N * s.P * s.Q * s.Cout;
@@ -937,8 +963,8 @@ static int conv_dgrad_run(Run& r, const ConvShape& s, const void* dy, const void
             }
         }
     }
-    if (r.dt == HS_BF16 && s.stride == 1) return gemm_splitk(r, p);
-    CALL(r, gemm_impl(&p, r.s));
+    if (r.dt == HS_BF16 && s.stride == 1) return gemm_splitk(r, p, false, rg);
+    CALL(r, gemm_impl(&p, r.s, rg));
     return HS_OK;
 }
 static int conv_wgrad_run(Run& r, const ConvShape& s, const void* dy, const void* x, float* dw) {
@@ -1154,7 +1180,12 @@ static int resblock_bwd_run(Run& r, const hs_resblock_desc& d, const void* x, co
         if (i > 0) g_in[i] = r.ws.alloc((long long)d.N * b.s.H * b.s.W * b.s.Cin * es);
     }
     void* g_ds = d.has_ds ? r.ws.alloc(Mout * Cout * es) : nullptr;
-    void* dx_ds = (d.has_ds && dx) ? r.ws.alloc((long long)d.N * d.H * d.W * d.main[0].Cin * es) : nullptr;
+    // downsample data gradient: compact where the branch allows it (ds_compact).  A plan sizes the full buffer, so that one plan
+    // serves either setting of the switch.
+    const bool ds_cmp = d.has_ds && dx && ds_compact(r.dt, L.ds.s);
+    const long long ds_rows = (ds_cmp && !r.plan) ? (long long)d.N * L.ds.s.P * L.ds.s.Q : (long long)d.N * d.H * d.W;
+    void* dx_ds = (d.has_ds && dx) ? r.ws.alloc(ds_rows * d.main[0].Cin * es) : nullptr;
+    const ResGather ds_rg = {d.H, d.W};
     (void)max_act;
     for (int i = 0; i < d.n_main; ++i) HS_REQUIRE(d.main[i].Cout <= 4096, "resblock: Cout > 4096");
     HS_PROPAGATE(side_setup(r));
@@ -1195,7 +1226,7 @@ static int resblock_bwd_run(Run& r, const hs_resblock_desc& d, const void* x, co
         // downsample branch: identity = bn(conv(x)), no ReLU
         HS_PROPAGATE(bn_backward(d.ds, L.ds, Mout, dres, nullptr, 0, g_ds, nullptr));
         if (d.ds.dw) HS_PROPAGATE(on_side(r, [&]() { return conv_wgrad_run(r, L.ds.s, g_ds, x, d.ds.dw); }));
-        if (dx) HS_PROPAGATE(conv_dgrad_run(r, L.ds.s, g_ds, L.ds.w_c, dx_ds, nullptr));
+        if (dx) HS_PROPAGATE(conv_dgrad_run(r, L.ds.s, g_ds, L.ds.w_c, dx_ds, nullptr, nullptr, nullptr, ds_cmp));
         dres_for_x = dx_ds;
     }
     // walk the main path backwards
@@ -1204,7 +1235,7 @@ static int resblock_bwd_run(Run& r, const hs_resblock_desc& d, const void* x, co
         const void* in = i == 0 ? x : L.main[i - 1].a;
         if (d.main[i].dw) HS_PROPAGATE(on_side(r, [&]() { return conv_wgrad_run(r, b.s, g_conv[i], in, d.main[i].dw); }));
         if (i == 0) {
-            if (dx) HS_PROPAGATE(conv_dgrad_run(r, b.s, g_conv[i], b.w_c, dx, dres_for_x, next_bn));
+            if (dx) HS_PROPAGATE(conv_dgrad_run(r, b.s, g_conv[i], b.w_c, dx, dres_for_x, next_bn, ds_cmp ? &ds_rg : nullptr));
         } else {
             // the data gradient of stage i is d relu(bn(c)) of stage i - 1: its GEMM takes that BatchNorm's backward sums along
             const StageBuf& pb = L.main[i - 1];

@@ -187,7 +187,7 @@ struct Prepared {
     dim3 grid;
     double flops;
 };
-static int gemm_prepare(const hs_gemm_params* p, hipStream_t stream, Prepared& q, int force_cfg = -1) {
+static int gemm_prepare(const hs_gemm_params* p, hipStream_t stream, Prepared& q, int force_cfg = -1, const ResGather* rg = nullptr) {
     HS_REQUIRE(p != nullptr, "hs_gemm: null params");
     HS_REQUIRE(p->dtype == HS_F32 || p->dtype == HS_BF16, "hs_gemm: bad dtype %d", p->dtype);
     HS_REQUIRE(p->M > 0 && p->N > 0 && p->K >= 0, "hs_gemm: bad dims %d %d %d", p->M, p->N, p->K);
@@ -332,6 +332,21 @@ static int gemm_prepare(const hs_gemm_params* p, hipStream_t stream, Prepared& q
             a.div_sc = make_fastdiv(g.S * g.C);
             a.div_c = make_fastdiv(g.C);
         }
+    }
+    if (rg) {
+        // compact residual (ResGather): output rows are the pixels of an H x W grid, the residual holds the even ones.  A plain
+        // GEMM gets the row -> pixel divisors a data-gradient convolution already has; a parity-ordered one needs none.
+        HS_REQUIRE(bf16 && p->out_dtype == HS_BF16 && p->residual && !p->residual_before_act && batch == 1 && p->seg_rows <= 0 &&
+                       (combo <= 2 || combo == 4) && rg->H > 0 && rg->W > 0 && p->M % (rg->H * rg->W) == 0,
+                   "hs_gemm: a compact residual needs a bf16 GEMM or data-gradient convolution over whole H x W images, added after the activation");
+        if (conv) HS_REQUIRE(p->g.H == rg->H && p->g.W == rg->W, "hs_gemm: compact residual: grid mismatch");
+        else {
+            a.div_mhw = make_fastdiv(rg->H * rg->W);
+            a.div_mw = make_fastdiv(rg->W);
+        }
+        a.res_gather = 1;
+        a.res_p = (rg->H + 1) / 2;
+        a.res_q = (rg->W + 1) / 2;
     }
 
     // vector-path eligibility (16-byte chunks): strides and bases chunk aligned.
@@ -579,9 +594,10 @@ int gemm_bnb_finish_rows(const hs_gemm_params* p) {
     return q.a.tiles_m + stat_groups(q.a.tiles_m);
 }
 
-int gemm_impl(const hs_gemm_params* p, hipStream_t stream) {
+// rg (optional, internal callers only): the residual is compact, see ResGather
+int gemm_impl(const hs_gemm_params* p, hipStream_t stream, const ResGather* rg = nullptr) {
     Prepared q;
-    HS_PROPAGATE(gemm_prepare(p, stream, q));
+    HS_PROPAGATE(gemm_prepare(p, stream, q, -1, rg));
     const GemmArgs& a = q.a;
     const int cfg = q.cfg, combo = q.combo, split = q.split, batch = q.batch;
     const bool bf16 = q.bf16, conv = q.conv, vec = q.vec;

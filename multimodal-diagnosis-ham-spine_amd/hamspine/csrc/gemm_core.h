@@ -104,6 +104,11 @@ struct GemmArgs {
     // the 32-token chunks with a valid token, compacted to the front and zero-filled to the end of the last K tile; the K walk
     // ends behind column *k_cols (clamped to [one K tile, K]).  Set by the grouped queue alone: no other launch can carry it.
     const int* k_cols;
+    // Compact residual (ResGather, set by gemm_prepare alone): `residual` holds only the even pixels of the output grid, rows
+    // (n, h / 2, w / 2) of res_p x res_q pixels per image; an output row at an odd h or w adds +0.0f.  The row -> pixel split
+    // reuses div_mhw / div_mw (H * W, W); a parity-ordered launch needs none: its rows m < quarter ARE the compact rows in order.
+    int res_gather;
+    int res_p, res_q;
 };
 
 // stamp k of this workgroup: 0 start (clock taken at entry, stored together with stamp 1), 1 first DMA issued, 2 first tile landed (barrier passed), 3 K loop done,
@@ -131,6 +136,17 @@ __device__ __forceinline__ long long parity_row(const GemmArgs& a, int m) {   //
     unsigned n, h, w;
     parity_pixel(a, m, n, h, w);
     return ((long long)n * a.g.H + h) * a.g.W + w;
+}
+// compact residual (GemmArgs.res_gather): the row of the compact buffer that output row m adds, or -1 where it adds +0.0f.
+// m is the launch's own row index (the permuted one of a parity-ordered launch).
+__device__ __forceinline__ long long res_gather_row(const GemmArgs& a, int m, bool parity) {
+    if (parity) return m < a.quarter ? (long long)m : -1ll;      // class 0 = (even h, even w), in (n, h / 2, w / 2) order
+    const unsigned n = fdiv(m, a.div_mhw);
+    const unsigned hw = m - n * a.div_mhw.d;
+    const unsigned h = fdiv(hw, a.div_mw);
+    const unsigned w = hw - h * a.div_mw.d;
+    if ((h | w) & 1) return -1ll;
+    return ((long long)n * a.res_p + (h >> 1)) * a.res_q + (w >> 1);
 }
 
 
@@ -183,7 +199,8 @@ __device__ __forceinline__ void store4(char* base, long long idx, bool vec, int 
 enum {
     EPI_BIAS = 1, EPI_COLSCALE = 2, EPI_MUL_GELU = 4, EPI_MUL_RELU = 8, EPI_SEG = 16, EPI_PREACT = 32, EPI_RES_PRE = 64,
     EPI_RES_POST = 128, EPI_RELU = 256, EPI_GELU = 512, EPI_DROP = 1024, EPI_OUT_F32 = 2048, EPI_ACCUM = 4096, EPI_VEC = 8192,
-    EPI_PARITY = 16384, EPI_VEC16 = 32768
+    EPI_PARITY = 16384, EPI_VEC16 = 32768,
+    EPI_RES_GATHER = 65536     // with EPI_RES_POST: the residual is compact (GemmArgs.res_gather)
 };
 // The feature mask of a launch, computed once per workgroup.  (A struct holding copies of all epilogue arguments was tried
 // first: it ended up on the stack -- 120 B of scratch per lane, measured as 2.75x the algorithmic HBM write bytes of a GEMM
@@ -198,6 +215,7 @@ __device__ __forceinline__ unsigned epi_flags(const GemmArgs& a) {
     if (a.seg_rows > 0) f |= EPI_SEG;
     if (a.D_preact) f |= EPI_PREACT;
     if (a.residual) f |= a.res_pre_act ? EPI_RES_PRE : EPI_RES_POST;
+    if (a.residual && a.res_gather) f |= EPI_RES_GATHER;
     if (a.act == HS_ACT_RELU) f |= EPI_RELU;
     else if (a.act == HS_ACT_GELU) f |= EPI_GELU;
     if (a.drop_thresh) f |= EPI_DROP;
@@ -299,9 +317,19 @@ __device__ __forceinline__ void epilogue4(const GemmArgs& a, unsigned rt_flags, 
     }
     if (fl & EPI_RES_POST) {
         float r[4];
-        const long long ridx = dbase + mr * a.ldr + n;   // residual shares D's batch strides
-        if (out_f32) load4<float>(a.residual, ridx, vec, nvalid, r);
-        else load4<T>(a.residual, ridx, vec, nvalid, r);
+        if (fl & EPI_RES_GATHER) {
+            // compact residual (bf16 result, no batch): rows at an odd pixel add +0.0f -- the addition stays, a -0 accumulator
+            // leaves as +0 exactly as it does against the zero rows of a full-size residual
+            // (measured the same with every lane loading -- odd pixels reading row 0 and dropping it -- instead of the branch)
+            const long long rr = res_gather_row(a, m, fl & EPI_PARITY);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = 0.f;
+            if (rr >= 0) load4<T>(a.residual, rr * a.ldr + n, vec, nvalid, r);
+        } else {
+            const long long ridx = dbase + mr * a.ldr + n;   // residual shares D's batch strides
+            if (out_f32) load4<float>(a.residual, ridx, vec, nvalid, r);
+            else load4<T>(a.residual, ridx, vec, nvalid, r);
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] += r[j];
     }
@@ -1161,7 +1189,10 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& a, const int bx, 
                     if (live) {
                         pf_c[i][j] = *(const HS_GLOBAL u32x2*)((const HS_GLOBAL T*)a.bnb_x + (long long)m * a.ldd + n);
                         if (wy) pf_y[i][j] = *(const HS_GLOBAL u32x2*)((const HS_GLOBAL T*)a.bnb_y + (long long)m * a.ldd + n);
-                        if (wr) pf_r[i][j] = *(const HS_GLOBAL u32x2*)((const HS_GLOBAL T*)a.residual + (long long)m * a.ldr + n);
+                        if (wr) {
+                            const long long rr = a.res_gather ? res_gather_row(a, m, false) : (long long)m;   // (no parity order under the rider)
+                            if (rr >= 0) pf_r[i][j] = *(const HS_GLOBAL u32x2*)((const HS_GLOBAL T*)a.residual + rr * a.ldr + n);
+                        }
                     }
                 }
         }
@@ -1535,8 +1566,9 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& a, const int bx, 
                     if (from_y && live) {
                         load4<T>(a.bnb_y, (long long)m * a.ldd + n, true, 4, yv);
                         if (res_consumed) {
-                            float rv[4];
-                            load4<T>(a.residual, (long long)m * a.ldr + n, true, 4, rv);
+                            float rv[4] = {0.f, 0.f, 0.f, 0.f};
+                            const long long rr = a.res_gather ? res_gather_row(a, m, false) : (long long)m;
+                            if (rr >= 0) load4<T>(a.residual, rr * a.ldr + n, true, 4, rv);
 #pragma unroll
                             for (int e = 0; e < 4; ++e) acc[i][j][e] += rv[e];
                         }
@@ -1613,7 +1645,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& a, const int bx, 
     }
     // whole tile inside the matrix and 4-wide storable: one of the feature sets the training / inference steps use gets
     // branch-free code; anything else (edge tiles, rare combinations) takes the generic body
-    const unsigned epi_e = res_consumed ? (epi & ~(unsigned)EPI_RES_POST) : epi;     // (the sums' rider already added the residual)
+    const unsigned epi_e = res_consumed ? (epi & ~(unsigned)(EPI_RES_POST | EPI_RES_GATHER)) : epi;     // (the sums' rider already added the residual)
     int mdrop[FM];
 #pragma unroll
     for (int i = 0; i < FM; ++i) mdrop[i] = have_drow ? __shfl(drow_v[(i * 16) / 64], (i * 16 + l15) & 63, 64) : -1;
@@ -1634,6 +1666,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& a, const int bx, 
             HS_EPI_CASE(EPI_VEC | EPI_BIAS | EPI_DROP | EPI_RES_POST);                // dense + hidden dropout + residual
             HS_EPI_CASE(EPI_VEC | EPI_MUL_GELU);                                      // data gradient through GELU
             HS_EPI_CASE(EPI_VEC | EPI_RES_POST);                                      // data gradient + skip gradient
+            HS_EPI_CASE(EPI_VEC | EPI_RES_POST | EPI_RES_GATHER);                     // data gradient + compact downsample gradient
             HS_EPI_CASE(EPI_VEC | EPI_OUT_F32);                                       // weight gradient (f32)
             HS_EPI_CASE(EPI_VEC | EPI_OUT_F32 | EPI_SEG);                             // fused Q/K/V weight gradient
             HS_EPI_CASE(EPI_VEC | EPI_PARITY);                                        // stride-2 conv data gradient

@@ -356,7 +356,7 @@ inline bool p8_epilogue_supported(const GemmArgs& a) {
     if (a.accumulate) f |= EPI_ACCUM;
     if (a.vec_store) f |= EPI_VEC;
     if (a.parity) f |= EPI_PARITY;
-    if (a.epi_generic || a.alpha != 1.f) return false;
+    if (a.epi_generic || a.alpha != 1.f || a.res_gather) return false;
     if (!(f & EPI_OUT_F32) && !a.vec16) return false;
     switch (f) {
         case EPI_VEC: case EPI_VEC | EPI_BIAS: case EPI_VEC | EPI_BIAS | EPI_GELU | EPI_PREACT: case EPI_VEC | EPI_BIAS | EPI_RES_POST:

@@ -156,6 +156,14 @@ __device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) {
     return f.d <= 1 ? n : (__umulhi(n, f.mul) >> f.shr);
 }
 
+// Compact residual of a GEMM whose output rows are the pixels (n, h, w) of an H x W grid: the residual buffer holds only the
+// even pixels, as rows (n, h / 2, w / 2) -- the data gradient of a 1x1 pad-0 stride-2 convolution, which is zero everywhere
+// else.  Every other output row adds the constant +0.0f.  Internal to the composites: it travels as an extra argument of
+// gemm_impl (blocks.hip -> gemm.hip -> GemmArgs.res_gather), the C ABI has no such field.
+struct ResGather {
+    int H, W;
+};
+
 // ----------------------------------------------------------------------------------------------
 // counter-based dropout RNG: keep(i) is a pure function of (seed, element index), so forward and
 // backward regenerate the same mask without storing it.
