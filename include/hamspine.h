@@ -947,7 +947,8 @@ hs_status hs_resnet_bwd(const hs_resnet_desc* d, const void* const* dy_taps, voi
    ReLU output of the tower and of the stem's max-pool arg-max, in forward order: [0] stem BN+ReLU output ([N][P][Q][C],
    compute dtype), [1] max-pool arg-max taps (uint8 [N][P2][Q2][C], tap = 3*dh + dw inside the 3x3 window), then per block
    its inner stage outputs (n_main - 1 of them) and its output.  Returns the number of entries (-1: bad descriptor or
-   max_entries too small). */
+   max_entries too small).  In bf16 mode entry [0] may be UNWRITTEN: the training forward pools relu(bn(c)) straight from the
+   convolution output and never stores it (HAMSPINE_IMG_LEAN bit 0); the buffer stays reserved.  f32 mode always writes it. */
 int32_t hs_resnet_debug_offsets(const hs_resnet_desc* d, int64_t* out, int32_t max_entries);
 
 #define HS_BERT_MAX_LAYERS 24

@@ -27,6 +27,13 @@ int gemm_stat_rows(const hs_gemm_params* p);
 int gemm_bn_finish_rows(const hs_gemm_params* p);
 int gemm_tile_rows(const hs_gemm_params* p);
 int gemm_bnb_finish_rows(const hs_gemm_params* p);
+// lean forms of the image tower's BatchNorm / max-pool passes (norm.hip; bf16 only, see img_lean below)
+int bn_fwd_dsres(const hs_bn_params* p, const void* c_ds, const float* scale_ds, const float* shift_ds, hipStream_t s);
+int bn_relu_maxpool_fwd(const void* c, const float* scale, const float* shift, void* y, void* idx, int N, int H, int W, int C,
+                        hipStream_t s);
+int bn_bwd_pooled(const hs_bn_bwd_params* p, const void* idx, int N, int H, int W, hipStream_t s);
+long long bn_bwd_pair_ws_bytes(long long M, int C);
+int bn_bwd_pair(const hs_bn_bwd_params* p, const hs_bn_bwd_params* pd, hipStream_t s);
 void gemm_group_set_immediate_hook(int (*fn)(void*), void* ctx);
 struct GemmGroup;
 GemmGroup* gemm_group_open(hipStream_t s, long long slot);   // slot: any key that is stable across steps (its device table is cached)
@@ -765,6 +772,24 @@ static bool ds_compact(int dt, const ConvShape& s) {
     const char* e = getenv("HAMSPINE_DS_COMPACT");
     return !(e && e[0] == '0');
 }
+// HAMSPINE_IMG_LEAN: four places where the bf16 image tower used to write a full-size tensor only for the next elementwise kernel
+// to read it back; a bit mask, 0 = the separate launches, 15 = all four.  Read per call like HAMSPINE_DS_COMPACT.  The parts are
+// independent: no backward reads a buffer that only some setting of the forward writes (the stem backward in bf16 always takes
+// its ReLU mask from the convolution output).  The exact-f32 mode never takes these routes.
+// MEASURED (C2, six interleaved rounds, profiles/image_lean.txt): bits 0 / 2 / 3 bring 0.03 / 0.035 / 0.06 ms of step each, bit 1
+// none (its two gathering kernels take what the max-pool backward launch took): the default is 13, bit 1 stays off.
+enum {
+    IMG_LEAN_STEM_FWD = 1,   // stem: BatchNorm apply + ReLU + max-pool in one kernel, the activation is not stored
+    IMG_LEAN_STEM_BWD = 2,   // stem: BatchNorm backward gathers the max-pool gradient in registers, no full-size gradient map
+    IMG_LEAN_DS_FWD = 4,     // downsample identity formed inside the block output's apply pass, not stored
+    IMG_LEAN_DS_BWD = 8,     // last stage + downsample BatchNorm backward in one partial / final / apply, dres not stored
+    IMG_LEAN_DEFAULT = IMG_LEAN_STEM_FWD | IMG_LEAN_DS_FWD | IMG_LEAN_DS_BWD
+};
+static int img_lean(int dt) {
+    if (dt != HS_BF16) return 0;
+    const char* e = getenv("HAMSPINE_IMG_LEAN");
+    return e ? (atoi(e) & 15) : IMG_LEAN_DEFAULT;
+}
 static bool fused_ln_bwd_enabled() {        // HAMSPINE_FUSED_LN_BWD=0: separate LayerNorm-backward / dropout / column-sum passes
     static int v = -1;
     if (v < 0) {
@@ -1113,11 +1138,14 @@ static int resblock_fwd_run(Run& r, const hs_resblock_desc& d, const void* x, vo
         }
         return HS_OK;
     }
+    // lean: the downsample BatchNorm makes its statistics and scale / shift only; the last stage's apply pass forms the identity
+    // from L.ds.c itself and L.ds.a is not written
+    const bool ds_lean = d.has_ds && (img_lean(r.dt) & IMG_LEAN_DS_FWD);
     if (d.has_ds) {
         const long long Mo = (long long)d.N * L.ds.s.P * L.ds.s.Q;
         int srows = 0;
         hs_bn_params bp = bn_params(r, d, d.ds, L.ds, Mo);
-        bp.y = L.ds.a; bp.relu = 0;
+        bp.y = ds_lean ? nullptr : L.ds.a; bp.relu = 0;
         bp.ws = L.bn_ws; bp.ws_bytes = L.bn_ws_bytes;
         HS_PROPAGATE(conv_fwd_run(r, L.ds.s, x, L.ds.w_c, L.ds.c, d.training ? (float*)L.bn_ws : nullptr, &srows, nullptr, &bp));
         bp.partial_rows = srows;
@@ -1137,7 +1165,12 @@ static int resblock_fwd_run(Run& r, const hs_resblock_desc& d, const void* x, vo
         bp.ws = L.bn_ws; bp.ws_bytes = L.bn_ws_bytes;
         HS_PROPAGATE(conv_fwd_run(r, b.s, in, b.w_c, b.c, d.training ? (float*)L.bn_ws : nullptr, &srows, nullptr, &bp));
         bp.partial_rows = srows;
-        CALLK(r, 8, hs_batchnorm_fwd(&bp, r.s));
+        if (last && ds_lean) {
+            bp.residual = nullptr;
+            CALLK(r, 8, bn_fwd_dsres(&bp, L.ds.c, L.ds.scale, L.ds.shift, r.s));
+        } else {
+            CALLK(r, 8, hs_batchnorm_fwd(&bp, r.s));
+        }
         in = b.a;
     }
     return HS_OK;
@@ -1220,11 +1253,36 @@ static int resblock_bwd_run(Run& r, const hs_resblock_desc& d, const void* x, co
     };
 
     // last main stage: y = relu(bn(c_last) + identity)
-    HS_PROPAGATE(bn_backward(d.main[last], L.main[last], Mout, dy, y, 1, g_conv[last], dres, 0, own));
+    // lean: where this stage makes its own sums and the identity came through a downsample BatchNorm, one partial / final / apply
+    // serves both BatchNorms (bn_bwd_pair) and dres -- that branch's incoming gradient, dy or 0 -- is never stored.  The branch's
+    // sums and coefficients live in the idle dres buffer; where they would not fit (a few rows only) the separate passes run.
+    const bool pair = d.has_ds && !(own && own->rows > 0) && (img_lean(r.dt) & IMG_LEAN_DS_BWD) &&
+                      bn_bwd_pair_ws_bytes(Mout, Cout) <= std::min<long long>(Mout * Cout * es, L.bn_ws_bytes);
+    if (pair) {
+        hs_bn_bwd_params q[2];
+        memset(q, 0, sizeof(q));
+        const hs_conv_bn* cbs[2] = {&d.main[last], &d.ds};
+        const StageBuf* bs[2] = {&L.main[last], &L.ds};
+        for (int k = 0; k < 2; ++k) {
+            q[k].dtype = r.dt; q[k].C = Cout; q[k].M = Mout;
+            q[k].training = d.training;
+            q[k].x = bs[k]->c;
+            q[k].gamma = cbs[k]->gamma; q[k].save_mean = bs[k]->mean; q[k].save_invstd = bs[k]->invstd;
+            q[k].dgamma = cbs[k]->dgamma ? cbs[k]->dgamma : scratch_pg;
+            q[k].dbeta = cbs[k]->dbeta ? cbs[k]->dbeta : (scratch_pg ? scratch_pg + 4096 : nullptr);
+        }
+        q[0].relu = 1; q[0].dy = dy; q[0].y = y; q[0].dx = g_conv[last];
+        q[0].ws = L.bn_ws; q[0].ws_bytes = L.bn_ws_bytes;
+        q[1].dx = g_ds;
+        q[1].ws = dres; q[1].ws_bytes = Mout * Cout * es;
+        CALLK(r, 16, bn_bwd_pair(&q[0], &q[1], r.s));
+    } else {
+        HS_PROPAGATE(bn_backward(d.main[last], L.main[last], Mout, dy, y, 1, g_conv[last], dres, 0, own));
+    }
     const void* dres_for_x = dres;   // identity shortcut: dres flows straight into dx
     if (d.has_ds) {
         // downsample branch: identity = bn(conv(x)), no ReLU
-        HS_PROPAGATE(bn_backward(d.ds, L.ds, Mout, dres, nullptr, 0, g_ds, nullptr));
+        if (!pair) HS_PROPAGATE(bn_backward(d.ds, L.ds, Mout, dres, nullptr, 0, g_ds, nullptr));
         if (d.ds.dw) HS_PROPAGATE(on_side(r, [&]() { return conv_wgrad_run(r, L.ds.s, g_ds, x, d.ds.dw); }));
         if (dx) HS_PROPAGATE(conv_dgrad_run(r, L.ds.s, g_ds, L.ds.w_c, dx_ds, nullptr, nullptr, nullptr, ds_cmp));
         dres_for_x = dx_ds;
@@ -1364,6 +1422,14 @@ static int stem_fwd_run(Run& r, const hs_stem_desc& d, const float* image, void*
         }
     }
     CALL(r, gemm_impl(&p, r.s));
+    if (img_lean(r.dt) & IMG_LEAN_STEM_FWD) {
+        // lean: statistics and scale / shift only, then one kernel pools relu(bn(c)) straight from c; L.a is not written (the
+        // backward takes its ReLU mask from c)
+        bp.y = nullptr;
+        CALLK(r, 8, hs_batchnorm_fwd(&bp, r.s));
+        CALLK(r, 8, bn_relu_maxpool_fwd(L.c, L.scale, L.shift, y, L.idx, d.N, L.P, L.Q, cb.Cout, r.s));
+        return HS_OK;
+    }
     CALLK(r, 8, hs_batchnorm_fwd(&bp, r.s));
     CALL(r, hs_maxpool_fwd(r.dt, L.a, y, L.idx, d.N, L.P, L.Q, cb.Cout, 3, 2, 1, r.s));
     return HS_OK;
@@ -1380,7 +1446,8 @@ static int stem_bwd_run(Run& r, const hs_stem_desc& d, const void* y, const void
     float* dw_packed = (float*)r.ws.alloc((long long)cb.Cout * 224 * 4);
     RUN_CHECK_ARENAS(r, "stem_bwd");
     (void)y;
-    CALL(r, hs_maxpool_bwd(r.dt, dy, L.idx, da, d.N, L.P, L.Q, cb.Cout, 3, 2, 1, r.s));
+    const bool lean = img_lean(r.dt) & IMG_LEAN_STEM_BWD;   // the BatchNorm backward gathers the pooled gradient itself; da stays idle
+    if (!lean) CALL(r, hs_maxpool_bwd(r.dt, dy, L.idx, da, d.N, L.P, L.Q, cb.Cout, 3, 2, 1, r.s));
     hs_bn_bwd_params q;
     memset(&q, 0, sizeof(q));
     q.dtype = r.dt; q.C = cb.Cout; q.M = Mo;
@@ -1391,7 +1458,17 @@ static int stem_bwd_run(Run& r, const hs_stem_desc& d, const void* y, const void
     q.dgamma = cb.dgamma ? cb.dgamma : scratch_pg;
     q.dbeta = cb.dbeta ? cb.dbeta : (scratch_pg ? scratch_pg + 64 : nullptr);
     q.ws = L.bn_ws; q.ws_bytes = L.bn_ws_bytes;
-    CALLK(r, 16, hs_batchnorm_bwd(&q, r.s));
+    if (r.dt == HS_BF16) {          // bf16 never reads L.a: whatever HAMSPINE_IMG_LEAN was in the forward, the mask comes from c
+        q.y = nullptr;
+        q.scale = L.scale;
+        q.shift = L.shift;
+    }
+    if (lean) {
+        q.dy = dy;
+        CALLK(r, 16, bn_bwd_pooled(&q, L.idx, d.N, L.P, L.Q, r.s));
+    } else {
+        CALLK(r, 16, hs_batchnorm_bwd(&q, r.s));
+    }
     if (cb.dw) {
         hs_gemm_params p = gemm_defaults(r.dt);
         p.a_kind = HS_A_RC; p.b_kind = HS_B_CONV;

@@ -323,11 +323,11 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict
 // dx = ca*dz + cb*(x - mean) + cc per channel:  train  ca = g*is, cb = -g*is*is*dgamma/M, cc = -ca*dbeta/M
 //                                               eval   ca = g*is, cb = 0, cc = 0
 // (x - mean is formed first: folding mean into cc cancels catastrophically when |mean| >> std)
-__global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restrict__ ws, int gy, int C,
-                                                           const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                           const float* __restrict__ invstd, float invM, int train,
-                                                           float* __restrict__ dbeta, float* __restrict__ dgamma,
-                                                           float* __restrict__ coef) {
+__device__ __forceinline__ void bn_bwd_final_channel(const float* __restrict__ ws, int gy, int C,
+                                                     const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                     const float* __restrict__ invstd, float invM, int train,
+                                                     float* __restrict__ dbeta, float* __restrict__ dgamma,
+                                                     float* __restrict__ coef) {
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (c >= C) return;
@@ -349,6 +349,23 @@ __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restri
     coef[C + c] = cb;
     coef[2 * C + c] = cc;
     coef[3 * C + c] = mean[c];
+}
+__global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restrict__ ws, int gy, int C,
+                                                           const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                           const float* __restrict__ invstd, float invM, int train,
+                                                           float* __restrict__ dbeta, float* __restrict__ dgamma,
+                                                           float* __restrict__ coef) {
+    bn_bwd_final_channel(ws, gy, C, gamma, mean, invstd, invM, train, dbeta, dgamma, coef);
+}
+// two BatchNorms over the same [M][C] grid in one launch (blockIdx.y picks one): a block's last stage and its downsample branch
+struct BnFinalSet {
+    const float *ws, *gamma, *mean, *invstd;
+    float *dbeta, *dgamma, *coef;
+};
+__global__ __launch_bounds__(256) void bn_bwd_final_pair_kernel(BnFinalSet a, BnFinalSet b, int gy, int C, float invM, int train) {
+    const bool f = blockIdx.y == 0;      // (uniform selects of the pointers: no indexed copy of the argument structs)
+    bn_bwd_final_channel(f ? a.ws : b.ws, gy, C, f ? a.gamma : b.gamma, f ? a.mean : b.mean, f ? a.invstd : b.invstd, invM, train,
+                         f ? a.dbeta : b.dbeta, f ? a.dgamma : b.dgamma, f ? a.coef : b.coef);
 }
 // backward stage 2: dx = ca*dz + cb*x + cc (coefficients from bn_bwd_final_kernel); optional dres = dz
 template <typename T>
@@ -395,8 +412,366 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     }
 }
 
+// ============================================================================================
+// lean image-tower passes (bf16 composites only, HAMSPINE_IMG_LEAN in blocks.hip): the same arithmetic as the kernels above,
+// in the same order, with one full-size tensor less written to memory and read back.  Every value that used to cross memory
+// as bf16 is rounded to bf16 in registers, so the results are bitwise those of the separate launches.
+// ============================================================================================
+__device__ __forceinline__ float round_bf16(float v) { return (float)(bf16_t)v; }
+// bn_bwd_apply_kernel's  ca*dz + cb*(x - mu) + cc  as the compiler contracts it there: one product, one fma on top of it, one
+// add.  Which of the two products becomes the fma's addend is the compiler's choice per kernel, so the lean kernels spell the
+// chosen form out with contraction off -- left to it, the pair kernel took the other one and a few elements came out an ulp off.
+__device__ __forceinline__ float bn_bwd_dx(float ca, float dz, float cb, float x, float mu, float cc) {
+#pragma clang fp contract(off)
+    const float t = x - mu;
+    const float p = ca * dz;
+    const float f = fmaf(cb, t, p);
+    return f + cc;
+}
+
+// stem forward: y, idx = maxpool3x3/2(relu(bn(c))) straight from the convolution output -- bn_apply_kernel (relu) followed by
+// maxpool_fwd_kernel (elem.hip) without the activation in between: same window walk, first maximum wins, NaN propagates
+__global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const bf16_t* __restrict__ x, const float* __restrict__ scale,
+                                                              const float* __restrict__ shift, bf16_t* __restrict__ y,
+                                                              unsigned char* __restrict__ idx, int N, int H, int W, int C,
+                                                              int P, int Q) {
+    constexpr int E = 8, ks = 3, st = 2, pad = 1;
+    const int cg = C / E;
+    const long long total = (long long)N * P * Q * cg;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % cg);
+        long long t = i / cg;
+        const int q = (int)(t % Q);
+        t /= Q;
+        const int p = (int)(t % P);
+        const int n = (int)(t / P);
+        float best[E], sc[E], sf[E];
+        unsigned bi[E];
+#pragma unroll
+        for (int e = 0; e < E; e += 4) {
+            const f32x4 a = *(const f32x4*)(scale + c * E + e), b = *(const f32x4*)(shift + c * E + e);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                sc[e + j] = a[j];
+                sf[e + j] = b[j];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            best[e] = -INFINITY;
+            bi[e] = 0;
+        }
+#pragma unroll
+        for (int r = 0; r < ks; ++r) {
+            const int h = p * st - pad + r;
+            if ((unsigned)h >= (unsigned)H) continue;
+#pragma unroll
+            for (int s = 0; s < ks; ++s) {
+                const int w = q * st - pad + s;
+                if ((unsigned)w >= (unsigned)W) continue;
+                float f[E];
+                Chunk<bf16_t>::unpack(*(const u32x4*)(x + (((long long)n * H + h) * W + w) * C + c * E), f);
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const float v = round_bf16(fmaxf(fmaf(f[e], sc[e], sf[e]), 0.f));   // what bn_apply_kernel stores
+                    if (v > best[e] || v != v) {
+                        best[e] = v;
+                        bi[e] = (unsigned)(r * ks + s);
+                    }
+                }
+            }
+        }
+        const long long o = (((long long)n * P + p) * Q + q) * C + c * E;
+        *(u32x4*)(y + o) = Chunk<bf16_t>::pack(best);
+        u32x2 ib;
+        ib[0] = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
+        ib[1] = bi[4] | (bi[5] << 8) | (bi[6] << 16) | (bi[7] << 24);
+        *(u32x2*)(idx + o) = ib;
+    }
+}
+
+// the value maxpool_bwd_kernel (elem.hip, 3x3 / 2, pad 1) stores at row (n, h, w) of the [N*H*W][C] map, chunk cc: up to four
+// (p, q) windows in its order, f32 adds, rounded to bf16
+struct PoolGeom {
+    int H, W, P, Q;
+};
+__device__ __forceinline__ void maxpool_grad_at(const bf16_t* __restrict__ dy, const unsigned char* __restrict__ idx,
+                                                const PoolGeom& pg, unsigned row, int C, int cc, float (&out)[8]) {
+    constexpr int E = 8, ks = 3, st = 2, pad = 1;
+    const int w = (int)(row % (unsigned)pg.W);
+    const unsigned t = row / (unsigned)pg.W;
+    const int h = (int)(t % (unsigned)pg.H);
+    const int n = (int)(t / (unsigned)pg.H);
+    float acc[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) acc[e] = 0.f;
+    const int p_lo = max(0, (h + pad - ks + st) / st), p_hi = min(pg.P - 1, (h + pad) / st);
+    const int q_lo = max(0, (w + pad - ks + st) / st), q_hi = min(pg.Q - 1, (w + pad) / st);
+    for (int p = p_lo; p <= p_hi; ++p)
+        for (int q = q_lo; q <= q_hi; ++q) {
+            const int r = h + pad - p * st, s = w + pad - q * st;
+            if (r < 0 || r >= ks || s < 0 || s >= ks) continue;
+            const unsigned me = (unsigned)(r * ks + s);
+            const long long o = (((long long)n * pg.P + p) * pg.Q + q) * C + cc * E;
+            float g[E];
+            Chunk<bf16_t>::unpack(*(const u32x4*)(dy + o), g);
+            const u32x2 ib = *(const u32x2*)(idx + o);
+#pragma unroll
+            for (int e = 0; e < E; ++e)
+                if (((ib[e >> 2] >> (8 * (e & 3))) & 0xffu) == me) acc[e] += g[e];
+        }
+#pragma unroll
+    for (int e = 0; e < E; ++e) out[e] = round_bf16(acc[e]);
+}
+
+// bn_bwd_partial_kernel with relu = 1, the mask recomputed from x, and dy taken through the max-pool gather
+__global__ __launch_bounds__(256) void bn_bwd_partial_pooled_kernel(const bf16_t* __restrict__ dyp,
+                                                                    const unsigned char* __restrict__ idx, PoolGeom pg,
+                                                                    const bf16_t* __restrict__ x, const float* __restrict__ mean,
+                                                                    const float* __restrict__ invstd, long long M, int C,
+                                                                    int tpc, float* __restrict__ ws,
+                                                                    const float* __restrict__ scale, const float* __restrict__ shift) {
+    constexpr int E = 8;
+    const int cg = C / E;
+    const int tx = threadIdx.x % tpc, ty = threadIdx.x / tpc, rows_par = 256 / tpc;
+    const int cc = blockIdx.x * tpc + tx;
+    float acc[2][E], mu[E], is[E], sc[E], sf[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) acc[0][e] = acc[1][e] = mu[e] = is[e] = sc[e] = sf[e] = 0.f;
+    if (cc < cg) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            mu[e] = mean[cc * E + e];
+            is[e] = invstd[cc * E + e];
+            sc[e] = scale[cc * E + e];
+            sf[e] = shift[cc * E + e];
+        }
+        const long long step = (long long)gridDim.y * rows_par;
+        long long r = (long long)blockIdx.y * rows_par + ty;
+        auto row = [&](long long rr, float (&g)[E], float (&xv)[E], float (&yv)[E]) {
+            const long long o = rr * C + (long long)cc * E;
+            maxpool_grad_at(dyp, idx, pg, (unsigned)rr, C, cc, g);
+            Chunk<bf16_t>::unpack(*(const u32x4*)(x + o), xv);
+#pragma unroll
+            for (int e = 0; e < E; ++e) yv[e] = fmaf(xv[e], sc[e], sf[e]);
+        };
+        auto fold = [&](const float (&g)[E], const float (&xv)[E], const float (&yv)[E]) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const float dz = !(yv[e] > 0.f) ? 0.f : g[e];
+                acc[0][e] += dz;
+                acc[1][e] = fmaf(dz, (xv[e] - mu[e]) * is[e], acc[1][e]);
+            }
+        };
+        for (; r + step < M; r += 2 * step) {
+            float g0[E], x0[E], y0[E], g1[E], x1[E], y1[E];
+            row(r, g0, x0, y0);
+            row(r + step, g1, x1, y1);
+            fold(g0, x0, y0);
+            fold(g1, x1, y1);
+        }
+        for (; r < M; r += step) {
+            float g0[E], x0[E], y0[E];
+            row(r, g0, x0, y0);
+            fold(g0, x0, y0);
+        }
+    }
+    __shared__ float sh[256 * E * 2];
+    block_col_reduce<E, 2>(acc, tpc, sh);
+    if (ty == 0 && cc < cg) {
+        float* o = ws + ((long long)blockIdx.y * C + (long long)cc * E) * 2;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            o[e * 2 + 0] = acc[0][e];
+            o[e * 2 + 1] = acc[1][e];
+        }
+    }
+}
+// bn_bwd_apply_kernel likewise (relu = 1, mask from x, no dres)
+__global__ __launch_bounds__(256) void bn_bwd_apply_pooled_kernel(const bf16_t* __restrict__ dyp,
+                                                                  const unsigned char* __restrict__ idx, PoolGeom pg,
+                                                                  const bf16_t* __restrict__ x, const float* __restrict__ coef,
+                                                                  bf16_t* __restrict__ dx, long long nchunks, int cg, int C,
+                                                                  const float* __restrict__ scale, const float* __restrict__ shift) {
+    constexpr int E = 8;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nchunks; i += (long long)gridDim.x * 256) {
+        const int ci = (int)(i % cg);
+        const int c0 = ci * E;
+        float g[E], xv[E], yv[E], o[E], ca[E], cb[E], cc[E], mu[E];
+        maxpool_grad_at(dyp, idx, pg, (unsigned)(i / cg), C, ci, g);
+        Chunk<bf16_t>::unpack(*(const u32x4*)(x + i * E), xv);
+#pragma unroll
+        for (int e = 0; e < E; ++e) yv[e] = fmaf(xv[e], scale[c0 + e], shift[c0 + e]);
+#pragma unroll
+        for (int e = 0; e < E; e += 4) {
+            const f32x4 a = *(const f32x4*)(coef + c0 + e), b = *(const f32x4*)(coef + C + c0 + e),
+                        c = *(const f32x4*)(coef + 2 * C + c0 + e), m = *(const f32x4*)(coef + 3 * C + c0 + e);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                ca[e + j] = a[j];
+                cb[e + j] = b[j];
+                cc[e + j] = c[j];
+                mu[e + j] = m[j];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const float dz = !(yv[e] > 0.f) ? 0.f : g[e];
+            o[e] = bn_bwd_dx(ca[e], dz, cb[e], xv[e], mu[e], cc[e]);
+        }
+        *(u32x4*)(dx + i * E) = Chunk<bf16_t>::pack(o);
+    }
+}
+
+// block output with a downsample identity: y = relu(fma(x, scale, shift) + bf16(fma(xd, scale_d, shift_d))) -- bn_apply_kernel
+// with the residual formed from the downsample convolution's output instead of read back from a stored identity
+__global__ __launch_bounds__(256) void bn_apply_dsres_kernel(const bf16_t* __restrict__ x, const float* __restrict__ scale,
+                                                             const float* __restrict__ shift, const bf16_t* __restrict__ xd,
+                                                             const float* __restrict__ scale_d, const float* __restrict__ shift_d,
+                                                             bf16_t* __restrict__ y, long long nchunks, int cg, int relu) {
+    constexpr int E = 8;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nchunks; i += (long long)gridDim.x * 256) {
+        const int c0 = (int)(i % cg) * E;
+        float f[E], r[E], sc[E], sh[E], sd[E], hd[E];
+        Chunk<bf16_t>::unpack(*(const u32x4*)(x + i * E), f);
+        Chunk<bf16_t>::unpack(*(const u32x4*)(xd + i * E), r);
+#pragma unroll
+        for (int e = 0; e < E; e += 4) {
+            const f32x4 a = *(const f32x4*)(scale + c0 + e), b = *(const f32x4*)(shift + c0 + e);
+            const f32x4 ad = *(const f32x4*)(scale_d + c0 + e), bd = *(const f32x4*)(shift_d + c0 + e);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                sc[e + j] = a[j];
+                sh[e + j] = b[j];
+                sd[e + j] = ad[j];
+                hd[e + j] = bd[j];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            float v = fmaf(f[e], sc[e], sh[e]);
+            v += round_bf16(fmaf(r[e], sd[e], hd[e]));
+            if (relu) v = fmaxf(v, 0.f);
+            f[e] = v;
+        }
+        *(u32x4*)(y + i * E) = Chunk<bf16_t>::pack(f);
+    }
+}
+
+// a block's last stage (relu, mask y > 0) and its downsample BatchNorm (no relu) in one pass: dz of the last stage is the
+// downsample branch's incoming gradient, known before any coefficient is.  Sums [0..1] are bn_bwd_partial_kernel's of the last
+// stage, sums of the downsample branch are what it makes with relu = 0 over the stored dres: same rows per thread, same order
+__global__ __launch_bounds__(256) void bn_bwd_partial_pair_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ y,
+                                                                  const bf16_t* __restrict__ x, const float* __restrict__ mean,
+                                                                  const float* __restrict__ invstd, const bf16_t* __restrict__ xd,
+                                                                  const float* __restrict__ mean_d,
+                                                                  const float* __restrict__ invstd_d, long long M, int C, int tpc,
+                                                                  float* __restrict__ ws, float* __restrict__ ws_d) {
+    constexpr int E = 8;
+    const int cg = C / E;
+    const int tx = threadIdx.x % tpc, ty = threadIdx.x / tpc, rows_par = 256 / tpc;
+    const int cc = blockIdx.x * tpc + tx;
+    float acc[2][E], accd[2][E], mu[E], is[E], mud[E], isd[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) acc[0][e] = acc[1][e] = accd[0][e] = accd[1][e] = mu[e] = is[e] = mud[e] = isd[e] = 0.f;
+    if (cc < cg) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            mu[e] = mean[cc * E + e];
+            is[e] = invstd[cc * E + e];
+            mud[e] = mean_d[cc * E + e];
+            isd[e] = invstd_d[cc * E + e];
+        }
+        const long long step = (long long)gridDim.y * rows_par;
+        long long r = (long long)blockIdx.y * rows_par + ty;
+        auto row = [&](long long rr, float (&g)[E], float (&xv)[E], float (&yv)[E], float (&dv)[E]) {
+            const long long o = rr * C + (long long)cc * E;
+            Chunk<bf16_t>::unpack(*(const u32x4*)(dy + o), g);
+            Chunk<bf16_t>::unpack(*(const u32x4*)(x + o), xv);
+            Chunk<bf16_t>::unpack(*(const u32x4*)(y + o), yv);
+            Chunk<bf16_t>::unpack(*(const u32x4*)(xd + o), dv);
+        };
+        auto fold = [&](const float (&g)[E], const float (&xv)[E], const float (&yv)[E], const float (&dv)[E]) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const float dz = !(yv[e] > 0.f) ? 0.f : g[e];     // exactly dy or 0: what the apply pass would store as dres
+                acc[0][e] += dz;
+                acc[1][e] = fmaf(dz, (xv[e] - mu[e]) * is[e], acc[1][e]);
+                accd[0][e] += dz;
+                accd[1][e] = fmaf(dz, (dv[e] - mud[e]) * isd[e], accd[1][e]);
+            }
+        };
+        for (; r + step < M; r += 2 * step) {
+            float g0[E], x0[E], y0[E], d0[E], g1[E], x1[E], y1[E], d1[E];
+            row(r, g0, x0, y0, d0);
+            row(r + step, g1, x1, y1, d1);
+            fold(g0, x0, y0, d0);
+            fold(g1, x1, y1, d1);
+        }
+        for (; r < M; r += step) {
+            float g0[E], x0[E], y0[E], d0[E];
+            row(r, g0, x0, y0, d0);
+            fold(g0, x0, y0, d0);
+        }
+    }
+    __shared__ float sh[256 * E * 2];
+    block_col_reduce<E, 2>(acc, tpc, sh);
+    __syncthreads();
+    block_col_reduce<E, 2>(accd, tpc, sh);
+    if (ty == 0 && cc < cg) {
+        float* o = ws + ((long long)blockIdx.y * C + (long long)cc * E) * 2;
+        float* od = ws_d + ((long long)blockIdx.y * C + (long long)cc * E) * 2;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            o[e * 2 + 0] = acc[0][e];
+            o[e * 2 + 1] = acc[1][e];
+            od[e * 2 + 0] = accd[0][e];
+            od[e * 2 + 1] = accd[1][e];
+        }
+    }
+}
+// both apply passes: dx of the last stage and dx_d of the downsample BatchNorm (its dy is dz); dres is not stored
+__global__ __launch_bounds__(256) void bn_bwd_apply_pair_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ y,
+                                                                const bf16_t* __restrict__ x, const float* __restrict__ coef,
+                                                                const bf16_t* __restrict__ xd, const float* __restrict__ coef_d,
+                                                                bf16_t* __restrict__ dx, bf16_t* __restrict__ dx_d,
+                                                                long long nchunks, int cg, int C) {
+    constexpr int E = 8;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nchunks; i += (long long)gridDim.x * 256) {
+        const int c0 = (int)(i % cg) * E;
+        float g[E], xv[E], yv[E], dv[E], o[E], od[E];
+        Chunk<bf16_t>::unpack(*(const u32x4*)(dy + i * E), g);
+        Chunk<bf16_t>::unpack(*(const u32x4*)(x + i * E), xv);
+        Chunk<bf16_t>::unpack(*(const u32x4*)(y + i * E), yv);
+        Chunk<bf16_t>::unpack(*(const u32x4*)(xd + i * E), dv);
+#pragma unroll
+        for (int e = 0; e < E; ++e) g[e] = !(yv[e] > 0.f) ? 0.f : g[e];
+#pragma unroll
+        for (int e = 0; e < E; e += 4) {
+            const f32x4 a = *(const f32x4*)(coef + c0 + e), b = *(const f32x4*)(coef + C + c0 + e),
+                        c = *(const f32x4*)(coef + 2 * C + c0 + e), m = *(const f32x4*)(coef + 3 * C + c0 + e);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[e + j] = bn_bwd_dx(a[j], g[e + j], b[j], xv[e + j], m[j], c[j]);
+        }
+#pragma unroll
+        for (int e = 0; e < E; e += 4) {
+            const f32x4 a = *(const f32x4*)(coef_d + c0 + e), b = *(const f32x4*)(coef_d + C + c0 + e),
+                        c = *(const f32x4*)(coef_d + 2 * C + c0 + e), m = *(const f32x4*)(coef_d + 3 * C + c0 + e);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) od[e + j] = bn_bwd_dx(a[j], g[e + j], b[j], dv[e + j], m[j], c[j]);
+        }
+        *(u32x4*)(dx + i * E) = Chunk<bf16_t>::pack(o);
+        *(u32x4*)(dx_d + i * E) = Chunk<bf16_t>::pack(od);
+    }
+}
+
+// dsr (optional, bf16): the residual is bf16(fma(dsr->c, dsr->scale, dsr->shift)), formed in the apply pass (bn_apply_dsres_kernel)
+struct DsResidual {
+    const void* c;
+    const float *scale, *shift;
+};
 template <typename T>
-static int bn_fwd_t(const hs_bn_params* p, hipStream_t s) {
+static int bn_fwd_t(const hs_bn_params* p, hipStream_t s, const DsResidual* dsr = nullptr) {
     constexpr int E = Chunk<T>::N;
     HS_REQUIRE(p->C % E == 0, "bn: C %% %d != 0", E);
     const long long M = p->M;
@@ -427,6 +802,12 @@ static int bn_fwd_t(const hs_bn_params* p, hipStream_t s) {
     if (p->y) {
         const long long nch = M * C / E;
         const int blocks = (int)std::min<long long>((nch + 255) / 256, 4096);
+        if (dsr) {
+            hipLaunchKernelGGL(bn_apply_dsres_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)p->x, p->scale, p->shift,
+                               (const bf16_t*)dsr->c, dsr->scale, dsr->shift, (bf16_t*)p->y, nch, C / E, p->relu);
+            HS_LAUNCH_CHECK();
+            return HS_OK;
+        }
         hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(blocks), dim3(256), 0, s, (const T*)p->x, p->scale, p->shift,
                            (const T*)p->residual, (T*)p->y, nch, C / E, p->relu);
         HS_LAUNCH_CHECK();
@@ -473,6 +854,93 @@ int bn_bwd(const hs_bn_bwd_params* p, hipStream_t s) {
     HS_REQUIRE(!p->relu || p->y || (p->scale && p->shift && !p->dres),
                "bn_bwd: a fused ReLU needs the forward output y, or (no residual) the forward's scale / shift to recompute its sign");
     return p->dtype == HS_BF16 ? bn_bwd_t<bf16_t>(p, s) : bn_bwd_t<float>(p, s);
+}
+// ---- lean forms for the bf16 composites (blocks.hip, HAMSPINE_IMG_LEAN); not part of the C ABI ----
+int bn_fwd_dsres(const hs_bn_params* p, const void* c_ds, const float* scale_ds, const float* shift_ds, hipStream_t s) {
+    HS_REQUIRE(p && p->x && p->y && p->scale && p->shift && p->save_mean && p->save_invstd && c_ds && scale_ds && shift_ds && !p->residual,
+               "bn_fwd_dsres: null argument");
+    HS_REQUIRE(p->dtype == HS_BF16, "bn_fwd_dsres: bf16 only");
+    const DsResidual dsr = {c_ds, scale_ds, shift_ds};
+    return bn_fwd_t<bf16_t>(p, s, &dsr);
+}
+// y, idx = maxpool3x3/2 pad 1 of relu(fma(c, scale, shift)); c is [N][H][W][C] bf16
+int bn_relu_maxpool_fwd(const void* c, const float* scale, const float* shift, void* y, void* idx, int N, int H, int W, int C,
+                        hipStream_t s) {
+    HS_REQUIRE(c && scale && shift && y && idx, "bn_relu_maxpool_fwd: null argument");
+    HS_REQUIRE(C % 8 == 0 && ((uintptr_t)idx & 7) == 0, "bn_relu_maxpool_fwd: C %% 8 != 0 or unaligned arg-max buffer");
+    const int P = (H + 2 - 3) / 2 + 1, Q = (W + 2 - 3) / 2 + 1;
+    const long long total = (long long)N * P * Q * (C / 8);
+    const int blocks = (int)std::max<long long>(1, std::min<long long>((total + 255) / 256, 4096));
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)c, scale, shift, (bf16_t*)y,
+                       (unsigned char*)idx, N, H, W, C, P, Q);
+    HS_LAUNCH_CHECK();
+    return HS_OK;
+}
+// hs_batchnorm_bwd of relu(bn(x)) whose incoming gradient is the max-pool backward of p->dy ([N][P][Q][C], arg-max idx) over
+// the [N][H][W][C] map x: the gradient map is formed in registers.  relu = 1, the mask comes from x (p->scale / p->shift).
+int bn_bwd_pooled(const hs_bn_bwd_params* p, const void* idx, int N, int H, int W, hipStream_t s) {
+    HS_REQUIRE(p && p->dy && p->x && p->dbeta && p->dgamma && p->scale && p->shift && idx && !p->dres, "bn_bwd_pooled: null argument");
+    HS_REQUIRE(p->dtype == HS_BF16 && p->relu && p->C % 8 == 0 && ((uintptr_t)idx & 7) == 0, "bn_bwd_pooled: bf16, relu, C %% 8 == 0");
+    const long long M = p->M;
+    HS_REQUIRE(M == (long long)N * H * W && M < (1ll << 31), "bn_bwd_pooled: M != N*H*W");
+    const int C = p->C;
+    const PoolGeom pg = {H, W, (H + 2 - 3) / 2 + 1, (W + 2 - 3) / 2 + 1};
+    const ColGeom g = col_geom(M, C, 8);
+    HS_REQUIRE(p->ws && p->ws_bytes >= (long long)g.gy * C * 2 * 4 + 4ll * C * 4, "bn_bwd_pooled: workspace too small");
+    float* coef = (float*)p->ws + (long long)g.gy * C * 2;
+    hipLaunchKernelGGL(bn_bwd_partial_pooled_kernel, dim3(g.gx, g.gy), dim3(256), 0, s, (const bf16_t*)p->dy,
+                       (const unsigned char*)idx, pg, (const bf16_t*)p->x, p->save_mean, p->save_invstd, M, C, g.tpc,
+                       (float*)p->ws, p->scale, p->shift);
+    HS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, s, (const float*)p->ws, g.gy, C, p->gamma,
+                       p->save_mean, p->save_invstd, 1.f / (float)M, p->training, p->dbeta, p->dgamma, coef);
+    HS_LAUNCH_CHECK();
+    if (p->dx) {
+        const long long nch = M * C / 8;
+        const int blocks = (int)std::min<long long>((nch + 255) / 256, 4096);
+        hipLaunchKernelGGL(bn_bwd_apply_pooled_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)p->dy,
+                           (const unsigned char*)idx, pg, (const bf16_t*)p->x, coef, (bf16_t*)p->dx, nch, C / 8, C, p->scale,
+                           p->shift);
+        HS_LAUNCH_CHECK();
+    }
+    return HS_OK;
+}
+// workspace bytes one BatchNorm of bn_bwd_pair needs (partials + coefficients)
+long long bn_bwd_pair_ws_bytes(long long M, int C) {
+    const ColGeom g = col_geom(M, C, 8);
+    return ((long long)g.gy * C * 2 + 4ll * C) * 4;
+}
+// p: a block's last stage, y = relu(bn(x) + identity), mask y > 0; pd: the BatchNorm (no relu) of the downsample branch that made
+// the identity, whose incoming gradient is p's dz.  Three launches do what hs_batchnorm_bwd(p) (with dres) followed by
+// hs_batchnorm_bwd(pd) (dy = dres) do in six, and dres is never stored.  pd->dy and p->dres are not used.
+int bn_bwd_pair(const hs_bn_bwd_params* p, const hs_bn_bwd_params* pd, hipStream_t s) {
+    HS_REQUIRE(p && pd && p->dy && p->y && p->x && p->dx && p->dbeta && p->dgamma && pd->x && pd->dx && pd->dbeta && pd->dgamma,
+               "bn_bwd_pair: null argument");
+    HS_REQUIRE(p->dtype == HS_BF16 && pd->dtype == HS_BF16 && p->relu && !pd->relu && p->C == pd->C && p->M == pd->M && p->C % 8 == 0 &&
+                   p->training == pd->training && p->partial_rows <= 0,
+               "bn_bwd_pair: the two BatchNorms must share M, C and mode (bf16)");
+    const long long M = p->M;
+    const int C = p->C;
+    const ColGeom g = col_geom(M, C, 8);
+    const long long need = ((long long)g.gy * C * 2 + 4ll * C) * 4;
+    HS_REQUIRE(p->ws && pd->ws && p->ws_bytes >= need && pd->ws_bytes >= need, "bn_bwd_pair: workspace too small");
+    float* coef = (float*)p->ws + (long long)g.gy * C * 2;
+    float* coef_d = (float*)pd->ws + (long long)g.gy * C * 2;
+    hipLaunchKernelGGL(bn_bwd_partial_pair_kernel, dim3(g.gx, g.gy), dim3(256), 0, s, (const bf16_t*)p->dy, (const bf16_t*)p->y,
+                       (const bf16_t*)p->x, p->save_mean, p->save_invstd, (const bf16_t*)pd->x, pd->save_mean, pd->save_invstd, M, C,
+                       g.tpc, (float*)p->ws, (float*)pd->ws);
+    HS_LAUNCH_CHECK();
+    const BnFinalSet fa = {(const float*)p->ws, p->gamma, p->save_mean, p->save_invstd, p->dbeta, p->dgamma, coef};
+    const BnFinalSet fb = {(const float*)pd->ws, pd->gamma, pd->save_mean, pd->save_invstd, pd->dbeta, pd->dgamma, coef_d};
+    hipLaunchKernelGGL(bn_bwd_final_pair_kernel, dim3(ceil_div(C, 4), 2), dim3(256), 0, s, fa, fb, g.gy, C, 1.f / (float)M,
+                       p->training);
+    HS_LAUNCH_CHECK();
+    const long long nch = M * C / 8;
+    const int blocks = (int)std::min<long long>((nch + 255) / 256, 4096);
+    hipLaunchKernelGGL(bn_bwd_apply_pair_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)p->dy, (const bf16_t*)p->y,
+                       (const bf16_t*)p->x, coef, (const bf16_t*)pd->x, coef_d, (bf16_t*)p->dx, (bf16_t*)pd->dx, nch, C / 8, C);
+    HS_LAUNCH_CHECK();
+    return HS_OK;
 }
 long long bn_ws_bytes(long long M, int C, int dtype) {
     ColGeom g = col_geom(M, C, dtype == HS_BF16 ? 8 : 4);
