@@ -5,6 +5,7 @@
 // mibf_net/model_resnet.py:15) and torch.nn.LayerNorm (modules/fusion_blocks.py:17-34, heads.py:36,
 // transformers BertEmbeddings / BertSelfOutput / BertOutput LayerNorm, eps 1e-12).
 #include <algorithm>
+#include <type_traits>
 #include "hs_common.h"
 
 namespace hs {
@@ -218,27 +219,45 @@ __global__ void bn_eval_scale_kernel(int C, float eps, const float* gamma, const
     shift_out[c] = b - running_mean[c] * g * invstd;
 }
 
-// y = x*scale + shift (+ residual) (relu)
-template <typename T>
+// E consecutive per-channel floats (a chunk's channels: 16-byte aligned) read as f32x4
+template <int E>
+__device__ __forceinline__ void load_chan(const float* __restrict__ p, float (&v)[E]) {
+#pragma unroll
+    for (int e = 0; e < E; e += 4) {
+        const f32x4 a = *(const f32x4*)(p + e);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[e + j] = a[j];
+    }
+}
+__device__ __forceinline__ float round_bf16(float v) { return (float)(bf16_t)v; }
+
+// y = x*scale + shift (+ residual) (relu).  The residual is none (res == nullptr), stored (res), or with DSRES formed from the
+// downsample convolution's output res as bf16(fma(res, scale_d, shift_d)): what the downsample BatchNorm's own apply pass would
+// have stored as the identity, rounded to bf16 in registers and not read back (lean image-tower passes, see below)
+template <typename T, bool DSRES>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, const float* __restrict__ scale,
                                                        const float* __restrict__ shift, const T* __restrict__ res,
+                                                       const float* __restrict__ scale_d, const float* __restrict__ shift_d,
                                                        T* __restrict__ y, long long nchunks, int cg, int relu) {
     constexpr int E = Chunk<T>::N;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nchunks; i += (long long)gridDim.x * 256) {
         const int c0 = (int)(i % cg) * E;
         float f[E], r[E], sc[E], sh[E];
         Chunk<T>::unpack(*(const u32x4*)(x + i * E), f);
-        if (res) Chunk<T>::unpack(*(const u32x4*)(res + i * E), r);
+        if (DSRES || res) Chunk<T>::unpack(*(const u32x4*)(res + i * E), r);
+        load_chan(scale + c0, sc);
+        load_chan(shift + c0, sh);
+        if constexpr (DSRES) {
+            float sd[E], hd[E];
+            load_chan(scale_d + c0, sd);
+            load_chan(shift_d + c0, hd);
 #pragma unroll
-        for (int e = 0; e < E; e += 4) {
-            const f32x4 a = *(const f32x4*)(scale + c0 + e), b = *(const f32x4*)(shift + c0 + e);
-            sc[e] = a[0]; sc[e + 1] = a[1]; sc[e + 2] = a[2]; sc[e + 3] = a[3];
-            sh[e] = b[0]; sh[e + 1] = b[1]; sh[e + 2] = b[2]; sh[e + 3] = b[3];
+            for (int e = 0; e < E; ++e) r[e] = round_bf16(fmaf(r[e], sd[e], hd[e]));
         }
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             float v = fmaf(f[e], sc[e], sh[e]);        // (explicit: the backward recomputes this very value for the ReLU mask)
-            if (res) v += r[e];
+            if (DSRES || res) v += r[e];
             if (relu) v = fmaxf(v, 0.f);
             f[e] = v;
         }
@@ -246,80 +265,6 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, 
     }
 }
 
-// backward stage 1: per (row block, channel) sums of dz and dz*xhat, dz = dy * (y > 0 if relu)
-template <typename T>
-__global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict__ dy, const T* __restrict__ y,
-                                                             const T* __restrict__ x, const float* __restrict__ mean,
-                                                             const float* __restrict__ invstd, long long M, int C,
-                                                             int tpc, int relu, float* __restrict__ ws,
-                                                             const float* __restrict__ scale, const float* __restrict__ shift) {
-    // y == nullptr with relu: the forward output was relu(fma(x, scale, shift)) with no residual, so its sign is recomputed
-    // from x (one activation read less; bf16 rounding never turns a positive f32 into 0)
-    constexpr int E = Chunk<T>::N;
-    const int cg = C / E;
-    const int tx = threadIdx.x % tpc, ty = threadIdx.x / tpc, rows_par = 256 / tpc;
-    const int cc = blockIdx.x * tpc + tx;
-    const bool maskx = relu && y == nullptr;
-    float acc[2][E], mu[E], is[E], sc[E], sf[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) acc[0][e] = acc[1][e] = mu[e] = is[e] = sc[e] = sf[e] = 0.f;
-    if (cc < cg) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            mu[e] = mean[cc * E + e];
-            is[e] = invstd[cc * E + e];
-            if (maskx) {
-                sc[e] = scale[cc * E + e];
-                sf[e] = shift[cc * E + e];
-            }
-        }
-        const long long step = (long long)gridDim.y * rows_par;
-        long long r = (long long)blockIdx.y * rows_par + ty;
-        auto row = [&](long long rr, float (&g)[E], float (&xv)[E], float (&yv)[E]) {
-            const long long o = rr * C + (long long)cc * E;
-            Chunk<T>::unpack(*(const u32x4*)(dy + o), g);
-            Chunk<T>::unpack(*(const u32x4*)(x + o), xv);
-            if (relu) {
-                if (maskx) {
-#pragma unroll
-                    for (int e = 0; e < E; ++e) yv[e] = fmaf(xv[e], sc[e], sf[e]);
-                } else {
-                    Chunk<T>::unpack(*(const u32x4*)(y + o), yv);
-                }
-            }
-        };
-        auto fold = [&](const float (&g)[E], const float (&xv)[E], const float (&yv)[E]) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const float dz = (relu && !(yv[e] > 0.f)) ? 0.f : g[e];
-                acc[0][e] += dz;
-                acc[1][e] = fmaf(dz, (xv[e] - mu[e]) * is[e], acc[1][e]);
-            }
-        };
-        for (; r + step < M; r += 2 * step) {
-            float g0[E], x0[E], y0[E], g1[E], x1[E], y1[E];
-            row(r, g0, x0, y0);
-            row(r + step, g1, x1, y1);
-            fold(g0, x0, y0);
-            fold(g1, x1, y1);
-        }
-        for (; r < M; r += step) {
-            float g0[E], x0[E], y0[E];
-            row(r, g0, x0, y0);
-            fold(g0, x0, y0);
-        }
-    }
-    __shared__ float sh[256 * E * 2];
-    block_col_reduce<E, 2>(acc, tpc, sh);
-    if (ty == 0 && cc < cg) {
-        float* o = ws + ((long long)blockIdx.y * C + (long long)cc * E) * 2;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            o[e * 2 + 0] = acc[0][e];
-            o[e * 2 + 1] = acc[1][e];
-        }
-    }
-}
 // dx = ca*dz + cb*(x - mean) + cc per channel:  train  ca = g*is, cb = -g*is*is*dgamma/M, cc = -ca*dbeta/M
 //                                               eval   ca = g*is, cb = 0, cc = 0
 // (x - mean is formed first: folding mean into cc cancels catastrophically when |mean| >> std)
@@ -367,68 +312,12 @@ __global__ __launch_bounds__(256) void bn_bwd_final_pair_kernel(BnFinalSet a, Bn
     bn_bwd_final_channel(f ? a.ws : b.ws, gy, C, f ? a.gamma : b.gamma, f ? a.mean : b.mean, f ? a.invstd : b.invstd, invM, train,
                          f ? a.dbeta : b.dbeta, f ? a.dgamma : b.dgamma, f ? a.coef : b.coef);
 }
-// backward stage 2: dx = ca*dz + cb*x + cc (coefficients from bn_bwd_final_kernel); optional dres = dz
-template <typename T>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ dy, const T* __restrict__ y,
-                                                           const T* __restrict__ x, const float* __restrict__ coef,
-                                                           T* __restrict__ dx, T* __restrict__ dres, long long nchunks,
-                                                           int cg, int C, int relu, const float* __restrict__ scale,
-                                                           const float* __restrict__ shift) {
-    constexpr int E = Chunk<T>::N;
-    const bool maskx = relu && y == nullptr;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nchunks; i += (long long)gridDim.x * 256) {
-        const int c0 = (int)(i % cg) * E;
-        float g[E], xv[E], yv[E], o[E], ca[E], cb[E], cc[E], mu[E];
-        Chunk<T>::unpack(*(const u32x4*)(dy + i * E), g);
-        Chunk<T>::unpack(*(const u32x4*)(x + i * E), xv);
-        if (relu) {
-            if (maskx) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) yv[e] = fmaf(xv[e], scale[c0 + e], shift[c0 + e]);
-            } else {
-                Chunk<T>::unpack(*(const u32x4*)(y + i * E), yv);
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < E; e += 4) {
-            const f32x4 a = *(const f32x4*)(coef + c0 + e), b = *(const f32x4*)(coef + C + c0 + e),
-                        c = *(const f32x4*)(coef + 2 * C + c0 + e), m = *(const f32x4*)(coef + 3 * C + c0 + e);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ca[e + j] = a[j];
-                cb[e + j] = b[j];
-                cc[e + j] = c[j];
-                mu[e + j] = m[j];
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const float dz = (relu && !(yv[e] > 0.f)) ? 0.f : g[e];
-            g[e] = dz;
-            o[e] = ca[e] * dz + cb[e] * (xv[e] - mu[e]) + cc[e];
-        }
-        *(u32x4*)(dx + i * E) = Chunk<T>::pack(o);
-        if (dres) *(u32x4*)(dres + i * E) = Chunk<T>::pack(g);
-    }
-}
-
 // ============================================================================================
-// lean image-tower passes (bf16 composites only, HAMSPINE_IMG_LEAN in blocks.hip): the same arithmetic as the kernels above,
-// in the same order, with one full-size tensor less written to memory and read back.  Every value that used to cross memory
-// as bf16 is rounded to bf16 in registers, so the results are bitwise those of the separate launches.
+// lean image-tower passes (bf16 composites only, HAMSPINE_IMG_LEAN in blocks.hip): the arithmetic of the separate launches, in
+// the same order, with one full-size tensor less written to memory and read back.  Every value that used to cross memory as
+// bf16 is rounded to bf16 in registers, and the apply and backward passes are instantiations of the bodies the separate
+// launches run (bn_apply_kernel above, bn_bwd_partial_kernel / bn_bwd_apply_kernel below), so the results are bitwise theirs.
 // ============================================================================================
-__device__ __forceinline__ float round_bf16(float v) { return (float)(bf16_t)v; }
-// bn_bwd_apply_kernel's  ca*dz + cb*(x - mu) + cc  as the compiler contracts it there: one product, one fma on top of it, one
-// add.  Which of the two products becomes the fma's addend is the compiler's choice per kernel, so the lean kernels spell the
-// chosen form out with contraction off -- left to it, the pair kernel took the other one and a few elements came out an ulp off.
-__device__ __forceinline__ float bn_bwd_dx(float ca, float dz, float cb, float x, float mu, float cc) {
-#pragma clang fp contract(off)
-    const float t = x - mu;
-    const float p = ca * dz;
-    const float f = fmaf(cb, t, p);
-    return f + cc;
-}
-
 // stem forward: y, idx = maxpool3x3/2(relu(bn(c))) straight from the convolution output -- bn_apply_kernel (relu) followed by
 // maxpool_fwd_kernel (elem.hip) without the activation in between: same window walk, first maximum wins, NaN propagates
 __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const bf16_t* __restrict__ x, const float* __restrict__ scale,
@@ -447,15 +336,8 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const bf16_t* __re
         const int n = (int)(t / P);
         float best[E], sc[E], sf[E];
         unsigned bi[E];
-#pragma unroll
-        for (int e = 0; e < E; e += 4) {
-            const f32x4 a = *(const f32x4*)(scale + c * E + e), b = *(const f32x4*)(shift + c * E + e);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                sc[e + j] = a[j];
-                sf[e + j] = b[j];
-            }
-        }
+        load_chan(scale + c * E, sc);
+        load_chan(shift + c * E, sf);
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             best[e] = -INFINITY;
@@ -524,253 +406,193 @@ __device__ __forceinline__ void maxpool_grad_at(const bf16_t* __restrict__ dy, c
     for (int e = 0; e < E; ++e) out[e] = round_bf16(acc[e]);
 }
 
-// bn_bwd_partial_kernel with relu = 1, the mask recomputed from x, and dy taken through the max-pool gather
-__global__ __launch_bounds__(256) void bn_bwd_partial_pooled_kernel(const bf16_t* __restrict__ dyp,
-                                                                    const unsigned char* __restrict__ idx, PoolGeom pg,
-                                                                    const bf16_t* __restrict__ x, const float* __restrict__ mean,
-                                                                    const float* __restrict__ invstd, long long M, int C,
-                                                                    int tpc, float* __restrict__ ws,
-                                                                    const float* __restrict__ scale, const float* __restrict__ shift) {
-    constexpr int E = 8;
+// ============================================================================================
+// BatchNorm backward: one partial-sum body and one apply body.  Their compile-time parameters are the element type, where the
+// incoming gradient dy comes from (a gradient source, below) and whether a second BatchNorm fed by the same dz rides along (PAIR).
+// A new fused variant is one more gradient source (or residual source of bn_apply_kernel), never a copy of a kernel.
+// ============================================================================================
+// gradient sources: chunk cc of row `row` of the [M][C] gradient map, at element offset o = row * C + cc * E
+// relu_from_x: the ReLU mask is known at compile time to be recomputed from x (else the runtime relu / y == nullptr tests decide)
+struct GradStored {          // dy is the map itself
+    static constexpr bool relu_from_x = false;
+    template <typename T, int E>
+    __device__ __forceinline__ void load(const T* __restrict__ dy, long long o, long long, int, int, float (&g)[E]) const {
+        Chunk<T>::unpack(*(const u32x4*)(dy + o), g);
+    }
+};
+struct GradPooled {          // dy is the [N][P][Q][C] gradient of a 3x3 / 2 max-pool of the map: gathered, never stored (stem, bf16)
+    static constexpr bool relu_from_x = true;     // the stem is relu(bn(c)); with the runtime tests the gather costs an occupancy step
+    const unsigned char* idx;
+    PoolGeom pg;
+    __device__ __forceinline__ void load(const bf16_t* __restrict__ dy, long long, long long row, int cc, int C, float (&g)[8]) const {
+        maxpool_grad_at(dy, idx, pg, (unsigned)row, C, cc, g);
+    }
+};
+
+// backward stage 1: per (row block, channel) sums of dz and dz*xhat, dz = dy * (y > 0 if relu); bn_bwd_final_kernel merges them.
+// y == nullptr with relu: the forward output was relu(fma(x, scale, shift)) with no residual, so its sign is recomputed from x
+// (one activation read less; bf16 rounding never turns a positive f32 into 0).
+// PAIR: x is a block's last stage (relu, mask y > 0) and xd its downsample BatchNorm (no relu), whose incoming gradient is that dz
+// -- exactly dy or 0, what the apply pass would store as dres -- known before any coefficient is.  The second sums are what this
+// kernel makes alone with relu = 0 over the stored dres: same rows per thread, same order.
+template <typename T, typename Src, bool PAIR>
+__global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict__ dy, Src src, const T* __restrict__ y,
+                                                             const T* __restrict__ x, const float* __restrict__ mean,
+                                                             const float* __restrict__ invstd, long long M, int C,
+                                                             int tpc, int relu_arg, float* __restrict__ ws,
+                                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                                             const T* __restrict__ xd, const float* __restrict__ mean_d,
+                                                             const float* __restrict__ invstd_d, float* __restrict__ ws_d) {
+    constexpr int E = Chunk<T>::N, NB = PAIR ? 2 : 1;
     const int cg = C / E;
     const int tx = threadIdx.x % tpc, ty = threadIdx.x / tpc, rows_par = 256 / tpc;
     const int cc = blockIdx.x * tpc + tx;
-    float acc[2][E], mu[E], is[E], sc[E], sf[E];
+    // (PAIR is by definition relu with the mask from the stored y: a compile-time fact as well, or the runtime branches sit
+    // between the loads of the rows in flight -- the pair's partial pass took 58 us where the copy took 34)
+    const bool relu = PAIR || Src::relu_from_x || relu_arg, maskx = Src::relu_from_x || (!PAIR && relu && y == nullptr);
+    float acc[NB][2][E], mu[NB][E], is[NB][E], sc[E], sf[E];
 #pragma unroll
-    for (int e = 0; e < E; ++e) acc[0][e] = acc[1][e] = mu[e] = is[e] = sc[e] = sf[e] = 0.f;
+    for (int e = 0; e < E; ++e) {
+        sc[e] = sf[e] = 0.f;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[b][0][e] = acc[b][1][e] = mu[b][e] = is[b][e] = 0.f;
+    }
     if (cc < cg) {
 #pragma unroll
         for (int e = 0; e < E; ++e) {
-            mu[e] = mean[cc * E + e];
-            is[e] = invstd[cc * E + e];
-            sc[e] = scale[cc * E + e];
-            sf[e] = shift[cc * E + e];
+            mu[0][e] = mean[cc * E + e];
+            is[0][e] = invstd[cc * E + e];
+            if constexpr (PAIR) {
+                mu[1][e] = mean_d[cc * E + e];
+                is[1][e] = invstd_d[cc * E + e];
+            }
+            if (maskx) {
+                sc[e] = scale[cc * E + e];
+                sf[e] = shift[cc * E + e];
+            }
         }
         const long long step = (long long)gridDim.y * rows_par;
         long long r = (long long)blockIdx.y * rows_par + ty;
-        auto row = [&](long long rr, float (&g)[E], float (&xv)[E], float (&yv)[E]) {
+        auto load = [&](long long rr, float (&g)[E], float (&xv)[NB][E], float (&yv)[E]) {
             const long long o = rr * C + (long long)cc * E;
-            maxpool_grad_at(dyp, idx, pg, (unsigned)rr, C, cc, g);
-            Chunk<bf16_t>::unpack(*(const u32x4*)(x + o), xv);
+            src.load(dy, o, rr, cc, C, g);
+            Chunk<T>::unpack(*(const u32x4*)(x + o), xv[0]);
+            if (relu) {
+                if (maskx) {
 #pragma unroll
-            for (int e = 0; e < E; ++e) yv[e] = fmaf(xv[e], sc[e], sf[e]);
+                    for (int e = 0; e < E; ++e) yv[e] = fmaf(xv[0][e], sc[e], sf[e]);
+                } else {
+                    Chunk<T>::unpack(*(const u32x4*)(y + o), yv);
+                }
+            }
+            if constexpr (PAIR) Chunk<T>::unpack(*(const u32x4*)(xd + o), xv[1]);
         };
-        auto fold = [&](const float (&g)[E], const float (&xv)[E], const float (&yv)[E]) {
+        auto fold = [&](const float (&g)[E], const float (&xv)[NB][E], const float (&yv)[E]) {
 #pragma unroll
             for (int e = 0; e < E; ++e) {
-                const float dz = !(yv[e] > 0.f) ? 0.f : g[e];
-                acc[0][e] += dz;
-                acc[1][e] = fmaf(dz, (xv[e] - mu[e]) * is[e], acc[1][e]);
+                const float dz = (relu && !(yv[e] > 0.f)) ? 0.f : g[e];
+#pragma unroll
+                for (int b = 0; b < NB; ++b) {
+                    acc[b][0][e] += dz;
+                    acc[b][1][e] = fmaf(dz, (xv[b][e] - mu[b][e]) * is[b][e], acc[b][1][e]);
+                }
             }
         };
-        for (; r + step < M; r += 2 * step) {
-            float g0[E], x0[E], y0[E], g1[E], x1[E], y1[E];
-            row(r, g0, x0, y0);
-            row(r + step, g1, x1, y1);
+        for (; r + step < M; r += 2 * step) {      // two rows in flight (separate arrays: as one struct per row, 8 VGPRs more)
+            float g0[E], x0[NB][E], y0[E], g1[E], x1[NB][E], y1[E];
+            load(r, g0, x0, y0);
+            load(r + step, g1, x1, y1);
             fold(g0, x0, y0);
             fold(g1, x1, y1);
         }
         for (; r < M; r += step) {
-            float g0[E], x0[E], y0[E];
-            row(r, g0, x0, y0);
+            float g0[E], x0[NB][E], y0[E];
+            load(r, g0, x0, y0);
             fold(g0, x0, y0);
         }
     }
     __shared__ float sh[256 * E * 2];
-    block_col_reduce<E, 2>(acc, tpc, sh);
-    if (ty == 0 && cc < cg) {
-        float* o = ws + ((long long)blockIdx.y * C + (long long)cc * E) * 2;
 #pragma unroll
-        for (int e = 0; e < E; ++e) {
-            o[e * 2 + 0] = acc[0][e];
-            o[e * 2 + 1] = acc[1][e];
-        }
-    }
-}
-// bn_bwd_apply_kernel likewise (relu = 1, mask from x, no dres)
-__global__ __launch_bounds__(256) void bn_bwd_apply_pooled_kernel(const bf16_t* __restrict__ dyp,
-                                                                  const unsigned char* __restrict__ idx, PoolGeom pg,
-                                                                  const bf16_t* __restrict__ x, const float* __restrict__ coef,
-                                                                  bf16_t* __restrict__ dx, long long nchunks, int cg, int C,
-                                                                  const float* __restrict__ scale, const float* __restrict__ shift) {
-    constexpr int E = 8;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nchunks; i += (long long)gridDim.x * 256) {
-        const int ci = (int)(i % cg);
-        const int c0 = ci * E;
-        float g[E], xv[E], yv[E], o[E], ca[E], cb[E], cc[E], mu[E];
-        maxpool_grad_at(dyp, idx, pg, (unsigned)(i / cg), C, ci, g);
-        Chunk<bf16_t>::unpack(*(const u32x4*)(x + i * E), xv);
-#pragma unroll
-        for (int e = 0; e < E; ++e) yv[e] = fmaf(xv[e], scale[c0 + e], shift[c0 + e]);
-#pragma unroll
-        for (int e = 0; e < E; e += 4) {
-            const f32x4 a = *(const f32x4*)(coef + c0 + e), b = *(const f32x4*)(coef + C + c0 + e),
-                        c = *(const f32x4*)(coef + 2 * C + c0 + e), m = *(const f32x4*)(coef + 3 * C + c0 + e);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ca[e + j] = a[j];
-                cb[e + j] = b[j];
-                cc[e + j] = c[j];
-                mu[e + j] = m[j];
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const float dz = !(yv[e] > 0.f) ? 0.f : g[e];
-            o[e] = bn_bwd_dx(ca[e], dz, cb[e], xv[e], mu[e], cc[e]);
-        }
-        *(u32x4*)(dx + i * E) = Chunk<bf16_t>::pack(o);
-    }
-}
-
-// block output with a downsample identity: y = relu(fma(x, scale, shift) + bf16(fma(xd, scale_d, shift_d))) -- bn_apply_kernel
-// with the residual formed from the downsample convolution's output instead of read back from a stored identity
-__global__ __launch_bounds__(256) void bn_apply_dsres_kernel(const bf16_t* __restrict__ x, const float* __restrict__ scale,
-                                                             const float* __restrict__ shift, const bf16_t* __restrict__ xd,
-                                                             const float* __restrict__ scale_d, const float* __restrict__ shift_d,
-                                                             bf16_t* __restrict__ y, long long nchunks, int cg, int relu) {
-    constexpr int E = 8;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nchunks; i += (long long)gridDim.x * 256) {
-        const int c0 = (int)(i % cg) * E;
-        float f[E], r[E], sc[E], sh[E], sd[E], hd[E];
-        Chunk<bf16_t>::unpack(*(const u32x4*)(x + i * E), f);
-        Chunk<bf16_t>::unpack(*(const u32x4*)(xd + i * E), r);
-#pragma unroll
-        for (int e = 0; e < E; e += 4) {
-            const f32x4 a = *(const f32x4*)(scale + c0 + e), b = *(const f32x4*)(shift + c0 + e);
-            const f32x4 ad = *(const f32x4*)(scale_d + c0 + e), bd = *(const f32x4*)(shift_d + c0 + e);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                sc[e + j] = a[j];
-                sh[e + j] = b[j];
-                sd[e + j] = ad[j];
-                hd[e + j] = bd[j];
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            float v = fmaf(f[e], sc[e], sh[e]);
-            v += round_bf16(fmaf(r[e], sd[e], hd[e]));
-            if (relu) v = fmaxf(v, 0.f);
-            f[e] = v;
-        }
-        *(u32x4*)(y + i * E) = Chunk<bf16_t>::pack(f);
-    }
-}
-
-// a block's last stage (relu, mask y > 0) and its downsample BatchNorm (no relu) in one pass: dz of the last stage is the
-// downsample branch's incoming gradient, known before any coefficient is.  Sums [0..1] are bn_bwd_partial_kernel's of the last
-// stage, sums of the downsample branch are what it makes with relu = 0 over the stored dres: same rows per thread, same order
-__global__ __launch_bounds__(256) void bn_bwd_partial_pair_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ y,
-                                                                  const bf16_t* __restrict__ x, const float* __restrict__ mean,
-                                                                  const float* __restrict__ invstd, const bf16_t* __restrict__ xd,
-                                                                  const float* __restrict__ mean_d,
-                                                                  const float* __restrict__ invstd_d, long long M, int C, int tpc,
-                                                                  float* __restrict__ ws, float* __restrict__ ws_d) {
-    constexpr int E = 8;
-    const int cg = C / E;
-    const int tx = threadIdx.x % tpc, ty = threadIdx.x / tpc, rows_par = 256 / tpc;
-    const int cc = blockIdx.x * tpc + tx;
-    float acc[2][E], accd[2][E], mu[E], is[E], mud[E], isd[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) acc[0][e] = acc[1][e] = accd[0][e] = accd[1][e] = mu[e] = is[e] = mud[e] = isd[e] = 0.f;
-    if (cc < cg) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            mu[e] = mean[cc * E + e];
-            is[e] = invstd[cc * E + e];
-            mud[e] = mean_d[cc * E + e];
-            isd[e] = invstd_d[cc * E + e];
-        }
-        const long long step = (long long)gridDim.y * rows_par;
-        long long r = (long long)blockIdx.y * rows_par + ty;
-        auto row = [&](long long rr, float (&g)[E], float (&xv)[E], float (&yv)[E], float (&dv)[E]) {
-            const long long o = rr * C + (long long)cc * E;
-            Chunk<bf16_t>::unpack(*(const u32x4*)(dy + o), g);
-            Chunk<bf16_t>::unpack(*(const u32x4*)(x + o), xv);
-            Chunk<bf16_t>::unpack(*(const u32x4*)(y + o), yv);
-            Chunk<bf16_t>::unpack(*(const u32x4*)(xd + o), dv);
-        };
-        auto fold = [&](const float (&g)[E], const float (&xv)[E], const float (&yv)[E], const float (&dv)[E]) {
+    for (int b = 0; b < NB; ++b) {
+        if (b) __syncthreads();
+        block_col_reduce<E, 2>(acc[b], tpc, sh);
+        if (ty == 0 && cc < cg) {
+            float* o = (b ? ws_d : ws) + ((long long)blockIdx.y * C + (long long)cc * E) * 2;
 #pragma unroll
             for (int e = 0; e < E; ++e) {
-                const float dz = !(yv[e] > 0.f) ? 0.f : g[e];     // exactly dy or 0: what the apply pass would store as dres
-                acc[0][e] += dz;
-                acc[1][e] = fmaf(dz, (xv[e] - mu[e]) * is[e], acc[1][e]);
-                accd[0][e] += dz;
-                accd[1][e] = fmaf(dz, (dv[e] - mud[e]) * isd[e], accd[1][e]);
+                o[e * 2 + 0] = acc[b][0][e];
+                o[e * 2 + 1] = acc[b][1][e];
             }
-        };
-        for (; r + step < M; r += 2 * step) {
-            float g0[E], x0[E], y0[E], d0[E], g1[E], x1[E], y1[E], d1[E];
-            row(r, g0, x0, y0, d0);
-            row(r + step, g1, x1, y1, d1);
-            fold(g0, x0, y0, d0);
-            fold(g1, x1, y1, d1);
         }
-        for (; r < M; r += step) {
-            float g0[E], x0[E], y0[E], d0[E];
-            row(r, g0, x0, y0, d0);
-            fold(g0, x0, y0, d0);
-        }
-    }
-    __shared__ float sh[256 * E * 2];
-    block_col_reduce<E, 2>(acc, tpc, sh);
-    __syncthreads();
-    block_col_reduce<E, 2>(accd, tpc, sh);
-    if (ty == 0 && cc < cg) {
-        float* o = ws + ((long long)blockIdx.y * C + (long long)cc * E) * 2;
-        float* od = ws_d + ((long long)blockIdx.y * C + (long long)cc * E) * 2;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            o[e * 2 + 0] = acc[0][e];
-            o[e * 2 + 1] = acc[1][e];
-            od[e * 2 + 0] = accd[0][e];
-            od[e * 2 + 1] = accd[1][e];
-        }
-    }
-}
-// both apply passes: dx of the last stage and dx_d of the downsample BatchNorm (its dy is dz); dres is not stored
-__global__ __launch_bounds__(256) void bn_bwd_apply_pair_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ y,
-                                                                const bf16_t* __restrict__ x, const float* __restrict__ coef,
-                                                                const bf16_t* __restrict__ xd, const float* __restrict__ coef_d,
-                                                                bf16_t* __restrict__ dx, bf16_t* __restrict__ dx_d,
-                                                                long long nchunks, int cg, int C) {
-    constexpr int E = 8;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nchunks; i += (long long)gridDim.x * 256) {
-        const int c0 = (int)(i % cg) * E;
-        float g[E], xv[E], yv[E], dv[E], o[E], od[E];
-        Chunk<bf16_t>::unpack(*(const u32x4*)(dy + i * E), g);
-        Chunk<bf16_t>::unpack(*(const u32x4*)(x + i * E), xv);
-        Chunk<bf16_t>::unpack(*(const u32x4*)(y + i * E), yv);
-        Chunk<bf16_t>::unpack(*(const u32x4*)(xd + i * E), dv);
-#pragma unroll
-        for (int e = 0; e < E; ++e) g[e] = !(yv[e] > 0.f) ? 0.f : g[e];
-#pragma unroll
-        for (int e = 0; e < E; e += 4) {
-            const f32x4 a = *(const f32x4*)(coef + c0 + e), b = *(const f32x4*)(coef + C + c0 + e),
-                        c = *(const f32x4*)(coef + 2 * C + c0 + e), m = *(const f32x4*)(coef + 3 * C + c0 + e);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[e + j] = bn_bwd_dx(a[j], g[e + j], b[j], xv[e + j], m[j], c[j]);
-        }
-#pragma unroll
-        for (int e = 0; e < E; e += 4) {
-            const f32x4 a = *(const f32x4*)(coef_d + c0 + e), b = *(const f32x4*)(coef_d + C + c0 + e),
-                        c = *(const f32x4*)(coef_d + 2 * C + c0 + e), m = *(const f32x4*)(coef_d + 3 * C + c0 + e);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) od[e + j] = bn_bwd_dx(a[j], g[e + j], b[j], dv[e + j], m[j], c[j]);
-        }
-        *(u32x4*)(dx + i * E) = Chunk<bf16_t>::pack(o);
-        *(u32x4*)(dx_d + i * E) = Chunk<bf16_t>::pack(od);
     }
 }
 
-// dsr (optional, bf16): the residual is bf16(fma(dsr->c, dsr->scale, dsr->shift)), formed in the apply pass (bn_apply_dsres_kernel)
+// dx = ca*dz + cb*(x - mu) + cc, with contraction off: every BatchNorm backward forms dx here, so no result depends on how the
+// compiler would fuse the expression.  Left to it, it had fused it differently per kernel -- a copied lean kernel once came out
+// an ulp off the separate launches for that reason.  The two forms below are the ones it had chosen for the plain kernels (read
+// from their gfx950 assembly) and are now fixed, so bf16 and f32 results are bit for bit what they were:
+//   bf16 (8 elements per thread): fma(cb, x - mu, ca*dz) + cc      f32 (4 per thread): (ca*dz + cb*(x - mu)) + cc, nothing fused.
+// They differ for no numerical reason: it is where the optimiser's heuristics happened to land for the two chunk widths.
+template <typename T>
+__device__ __forceinline__ float bn_bwd_dx(float ca, float dz, float cb, float x, float mu, float cc) {
+#pragma clang fp contract(off)
+    const float t = x - mu;
+    const float p = ca * dz;
+    if constexpr (sizeof(T) == 2) return fmaf(cb, t, p) + cc;
+    else return (p + cb * t) + cc;
+}
+
+// backward stage 2: dx from the coefficients [ca | cb | cc | mean] of bn_bwd_final_kernel; optional dres = dz (the separate
+// launches only: the lean forms exist so that it is not stored).  PAIR: also dx_d of the downsample BatchNorm, whose dy is dz.
+template <typename T, typename Src, bool PAIR>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ dy, Src src, const T* __restrict__ y,
+                                                           const T* __restrict__ x, const float* __restrict__ coef,
+                                                           T* __restrict__ dx, T* __restrict__ dres, long long nchunks,
+                                                           int cg, int C, int relu_arg, const float* __restrict__ scale,
+                                                           const float* __restrict__ shift, const T* __restrict__ xd,
+                                                           const float* __restrict__ coef_d, T* __restrict__ dx_d) {
+    constexpr int E = Chunk<T>::N, NB = PAIR ? 2 : 1;
+    constexpr bool plain = !PAIR && std::is_same<Src, GradStored>::value;
+    const bool relu = PAIR || Src::relu_from_x || relu_arg, maskx = Src::relu_from_x || (!PAIR && relu && y == nullptr);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nchunks; i += (long long)gridDim.x * 256) {
+        const int ci = (int)(i % cg), c0 = ci * E;
+        float g[E], xv[NB][E], yv[E];
+        src.load(dy, i * E, i / cg, ci, C, g);
+        Chunk<T>::unpack(*(const u32x4*)(x + i * E), xv[0]);
+        if (relu) {
+            if (maskx) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) yv[e] = fmaf(xv[0][e], scale[c0 + e], shift[c0 + e]);
+            } else {
+                Chunk<T>::unpack(*(const u32x4*)(y + i * E), yv);
+            }
+        }
+        if constexpr (PAIR) Chunk<T>::unpack(*(const u32x4*)(xd + i * E), xv[1]);
+#pragma unroll
+        for (int e = 0; e < E; ++e) g[e] = (relu && !(yv[e] > 0.f)) ? 0.f : g[e];     // dz
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const float* __restrict__ cf = (b ? coef_d : coef) + c0;
+            float o[E], ca[E], cb[E], cc[E], mu[E];
+            load_chan(cf, ca);
+            load_chan(cf + C, cb);
+            load_chan(cf + 2 * C, cc);
+            load_chan(cf + 3 * C, mu);
+#pragma unroll
+            for (int e = 0; e < E; ++e) o[e] = bn_bwd_dx<T>(ca[e], g[e], cb[e], xv[b][e], mu[e], cc[e]);
+            *(u32x4*)((b ? dx_d : dx) + i * E) = Chunk<T>::pack(o);
+        }
+        if constexpr (plain)
+            if (dres) *(u32x4*)(dres + i * E) = Chunk<T>::pack(g);
+    }
+}
+
+// dsr (DSRES, bf16): the residual is bf16(fma(dsr->c, dsr->scale, dsr->shift)), formed in the apply pass (bn_apply_kernel, DSRES)
 struct DsResidual {
     const void* c;
     const float *scale, *shift;
 };
-template <typename T>
+template <typename T, bool DSRES = false>
 static int bn_fwd_t(const hs_bn_params* p, hipStream_t s, const DsResidual* dsr = nullptr) {
     constexpr int E = Chunk<T>::N;
     HS_REQUIRE(p->C % E == 0, "bn: C %% %d != 0", E);
@@ -802,44 +624,58 @@ static int bn_fwd_t(const hs_bn_params* p, hipStream_t s, const DsResidual* dsr 
     if (p->y) {
         const long long nch = M * C / E;
         const int blocks = (int)std::min<long long>((nch + 255) / 256, 4096);
-        if (dsr) {
-            hipLaunchKernelGGL(bn_apply_dsres_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)p->x, p->scale, p->shift,
-                               (const bf16_t*)dsr->c, dsr->scale, dsr->shift, (bf16_t*)p->y, nch, C / E, p->relu);
-            HS_LAUNCH_CHECK();
-            return HS_OK;
-        }
-        hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(blocks), dim3(256), 0, s, (const T*)p->x, p->scale, p->shift,
-                           (const T*)p->residual, (T*)p->y, nch, C / E, p->relu);
+        hipLaunchKernelGGL((bn_apply_kernel<T, DSRES>), dim3(blocks), dim3(256), 0, s, (const T*)p->x, p->scale, p->shift,
+                           (const T*)(DSRES ? dsr->c : p->residual), DSRES ? dsr->scale : nullptr, DSRES ? dsr->shift : nullptr,
+                           (T*)p->y, nch, C / E, p->relu);
         HS_LAUNCH_CHECK();
     }
     return HS_OK;
 }
 
-template <typename T>
-static int bn_bwd_t(const hs_bn_bwd_params* p, hipStream_t s) {
+// backward workspace of one BatchNorm: `rows` rows of per-channel (sum dz, sum dz*xhat) partials, then the coefficients
+// [ca | cb | cc | mean] (the layout the GEMM epilogue that finishes the sums writes as well, gemm_core.h)
+static long long bn_bwd_ws_bytes(long long rows, int C) { return (rows * C * 2 + 4ll * C) * 4; }
+
+// the backward of p -- and with PAIR of pd, the downsample BatchNorm fed by p's dz, in the same three launches: geometry,
+// workspace [partials | coef], then partial sums -> dbeta / dgamma / coefficients -> dx.  y: the stored forward output the ReLU
+// mask is taken from, nullptr = recomputed from x.  `who` names the entry point in the refusals.
+template <typename T, typename Src, bool PAIR>
+static int bn_bwd_run(const char* who, const hs_bn_bwd_params* p, const hs_bn_bwd_params* pd, const void* y, Src src, hipStream_t s) {
     constexpr int E = Chunk<T>::N;
-    HS_REQUIRE(p->C % E == 0, "bn_bwd: C %% %d != 0", E);
+    HS_REQUIRE(p->C % E == 0, "%s: C %% %d != 0", who, E);
     const long long M = p->M;
     const int C = p->C;
     ColGeom g = col_geom(M, C, E);
     if (p->partial_rows > 0) g.gy = p->partial_rows;       // the sums came with the data gradient (hs_gemm_params.bnb_partials)
-    HS_REQUIRE(p->ws && p->ws_bytes >= (long long)g.gy * C * 2 * 4 + 4ll * C * 4, "bn_bwd: workspace too small");
+    const long long need = bn_bwd_ws_bytes(g.gy, C);
+    HS_REQUIRE(p->ws && p->ws_bytes >= need && (!PAIR || (pd->ws && pd->ws_bytes >= need)), "%s: workspace too small", who);
     float* coef = (float*)p->ws + (long long)g.gy * C * 2;
+    float* coef_d = PAIR ? (float*)pd->ws + (long long)g.gy * C * 2 : nullptr;
     if (p->partial_rows <= 0) {
-        hipLaunchKernelGGL(bn_bwd_partial_kernel<T>, dim3(g.gx, g.gy), dim3(256), 0, s, (const T*)p->dy, (const T*)p->y,
-                           (const T*)p->x, p->save_mean, p->save_invstd, M, C, g.tpc, p->relu, (float*)p->ws, p->scale, p->shift);
+        hipLaunchKernelGGL((bn_bwd_partial_kernel<T, Src, PAIR>), dim3(g.gx, g.gy), dim3(256), 0, s, (const T*)p->dy, src, (const T*)y,
+                           (const T*)p->x, p->save_mean, p->save_invstd, M, C, g.tpc, p->relu, (float*)p->ws, p->scale, p->shift,
+                           PAIR ? (const T*)pd->x : nullptr, PAIR ? pd->save_mean : nullptr, PAIR ? pd->save_invstd : nullptr,
+                           PAIR ? (float*)pd->ws : nullptr);
         HS_LAUNCH_CHECK();
     }
     if (!(p->partial_rows > 0 && p->sums_done)) {          // (sums_done: the producing GEMM's last workgroups wrote dbeta / dgamma / coef)
-        hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, s, (const float*)p->ws, g.gy, C, p->gamma,
-                           p->save_mean, p->save_invstd, 1.f / (float)M, p->training, p->dbeta, p->dgamma, coef);
+        if constexpr (PAIR) {
+            const BnFinalSet fa = {(const float*)p->ws, p->gamma, p->save_mean, p->save_invstd, p->dbeta, p->dgamma, coef};
+            const BnFinalSet fb = {(const float*)pd->ws, pd->gamma, pd->save_mean, pd->save_invstd, pd->dbeta, pd->dgamma, coef_d};
+            hipLaunchKernelGGL(bn_bwd_final_pair_kernel, dim3(ceil_div(C, 4), 2), dim3(256), 0, s, fa, fb, g.gy, C, 1.f / (float)M,
+                               p->training);
+        } else {
+            hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, s, (const float*)p->ws, g.gy, C, p->gamma,
+                               p->save_mean, p->save_invstd, 1.f / (float)M, p->training, p->dbeta, p->dgamma, coef);
+        }
         HS_LAUNCH_CHECK();
     }
     if (p->dx) {
         const long long nch = M * C / E;
         const int blocks = (int)std::min<long long>((nch + 255) / 256, 4096);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(blocks), dim3(256), 0, s, (const T*)p->dy, (const T*)p->y,
-                           (const T*)p->x, coef, (T*)p->dx, (T*)p->dres, nch, C / E, C, p->relu, p->scale, p->shift);
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<T, Src, PAIR>), dim3(blocks), dim3(256), 0, s, (const T*)p->dy, src, (const T*)y,
+                           (const T*)p->x, coef, (T*)p->dx, (T*)p->dres, nch, C / E, C, p->relu, p->scale, p->shift,
+                           PAIR ? (const T*)pd->x : nullptr, coef_d, PAIR ? (T*)pd->dx : nullptr);
         HS_LAUNCH_CHECK();
     }
     return HS_OK;
@@ -853,7 +689,8 @@ int bn_bwd(const hs_bn_bwd_params* p, hipStream_t s) {
     HS_REQUIRE(p && p->dy && p->x && p->dbeta && p->dgamma, "bn_bwd: null argument");
     HS_REQUIRE(!p->relu || p->y || (p->scale && p->shift && !p->dres),
                "bn_bwd: a fused ReLU needs the forward output y, or (no residual) the forward's scale / shift to recompute its sign");
-    return p->dtype == HS_BF16 ? bn_bwd_t<bf16_t>(p, s) : bn_bwd_t<float>(p, s);
+    return p->dtype == HS_BF16 ? bn_bwd_run<bf16_t, GradStored, false>("bn_bwd", p, nullptr, p->y, GradStored{}, s)
+                               : bn_bwd_run<float, GradStored, false>("bn_bwd", p, nullptr, p->y, GradStored{}, s);
 }
 // ---- lean forms for the bf16 composites (blocks.hip, HAMSPINE_IMG_LEAN); not part of the C ABI ----
 int bn_fwd_dsres(const hs_bn_params* p, const void* c_ds, const float* scale_ds, const float* shift_ds, hipStream_t s) {
@@ -861,7 +698,7 @@ int bn_fwd_dsres(const hs_bn_params* p, const void* c_ds, const float* scale_ds,
                "bn_fwd_dsres: null argument");
     HS_REQUIRE(p->dtype == HS_BF16, "bn_fwd_dsres: bf16 only");
     const DsResidual dsr = {c_ds, scale_ds, shift_ds};
-    return bn_fwd_t<bf16_t>(p, s, &dsr);
+    return bn_fwd_t<bf16_t, true>(p, s, &dsr);
 }
 // y, idx = maxpool3x3/2 pad 1 of relu(fma(c, scale, shift)); c is [N][H][W][C] bf16
 int bn_relu_maxpool_fwd(const void* c, const float* scale, const float* shift, void* y, void* idx, int N, int H, int W, int C,
@@ -880,36 +717,14 @@ int bn_relu_maxpool_fwd(const void* c, const float* scale, const float* shift, v
 // the [N][H][W][C] map x: the gradient map is formed in registers.  relu = 1, the mask comes from x (p->scale / p->shift).
 int bn_bwd_pooled(const hs_bn_bwd_params* p, const void* idx, int N, int H, int W, hipStream_t s) {
     HS_REQUIRE(p && p->dy && p->x && p->dbeta && p->dgamma && p->scale && p->shift && idx && !p->dres, "bn_bwd_pooled: null argument");
-    HS_REQUIRE(p->dtype == HS_BF16 && p->relu && p->C % 8 == 0 && ((uintptr_t)idx & 7) == 0, "bn_bwd_pooled: bf16, relu, C %% 8 == 0");
-    const long long M = p->M;
-    HS_REQUIRE(M == (long long)N * H * W && M < (1ll << 31), "bn_bwd_pooled: M != N*H*W");
-    const int C = p->C;
-    const PoolGeom pg = {H, W, (H + 2 - 3) / 2 + 1, (W + 2 - 3) / 2 + 1};
-    const ColGeom g = col_geom(M, C, 8);
-    HS_REQUIRE(p->ws && p->ws_bytes >= (long long)g.gy * C * 2 * 4 + 4ll * C * 4, "bn_bwd_pooled: workspace too small");
-    float* coef = (float*)p->ws + (long long)g.gy * C * 2;
-    hipLaunchKernelGGL(bn_bwd_partial_pooled_kernel, dim3(g.gx, g.gy), dim3(256), 0, s, (const bf16_t*)p->dy,
-                       (const unsigned char*)idx, pg, (const bf16_t*)p->x, p->save_mean, p->save_invstd, M, C, g.tpc,
-                       (float*)p->ws, p->scale, p->shift);
-    HS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, s, (const float*)p->ws, g.gy, C, p->gamma,
-                       p->save_mean, p->save_invstd, 1.f / (float)M, p->training, p->dbeta, p->dgamma, coef);
-    HS_LAUNCH_CHECK();
-    if (p->dx) {
-        const long long nch = M * C / 8;
-        const int blocks = (int)std::min<long long>((nch + 255) / 256, 4096);
-        hipLaunchKernelGGL(bn_bwd_apply_pooled_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)p->dy,
-                           (const unsigned char*)idx, pg, (const bf16_t*)p->x, coef, (bf16_t*)p->dx, nch, C / 8, C, p->scale,
-                           p->shift);
-        HS_LAUNCH_CHECK();
-    }
-    return HS_OK;
+    HS_REQUIRE(p->dtype == HS_BF16 && p->relu && p->C % 8 == 0 && ((uintptr_t)idx & 7) == 0 && p->partial_rows <= 0,
+               "bn_bwd_pooled: bf16, relu, C %% 8 == 0");
+    HS_REQUIRE(p->M == (long long)N * H * W && p->M < (1ll << 31), "bn_bwd_pooled: M != N*H*W");
+    const GradPooled src = {(const unsigned char*)idx, {H, W, (H + 2 - 3) / 2 + 1, (W + 2 - 3) / 2 + 1}};
+    return bn_bwd_run<bf16_t, GradPooled, false>("bn_bwd_pooled", p, nullptr, nullptr, src, s);
 }
 // workspace bytes one BatchNorm of bn_bwd_pair needs (partials + coefficients)
-long long bn_bwd_pair_ws_bytes(long long M, int C) {
-    const ColGeom g = col_geom(M, C, 8);
-    return ((long long)g.gy * C * 2 + 4ll * C) * 4;
-}
+long long bn_bwd_pair_ws_bytes(long long M, int C) { return bn_bwd_ws_bytes(col_geom(M, C, 8).gy, C); }
 // p: a block's last stage, y = relu(bn(x) + identity), mask y > 0; pd: the BatchNorm (no relu) of the downsample branch that made
 // the identity, whose incoming gradient is p's dz.  Three launches do what hs_batchnorm_bwd(p) (with dres) followed by
 // hs_batchnorm_bwd(pd) (dy = dres) do in six, and dres is never stored.  pd->dy and p->dres are not used.
@@ -919,28 +734,7 @@ int bn_bwd_pair(const hs_bn_bwd_params* p, const hs_bn_bwd_params* pd, hipStream
     HS_REQUIRE(p->dtype == HS_BF16 && pd->dtype == HS_BF16 && p->relu && !pd->relu && p->C == pd->C && p->M == pd->M && p->C % 8 == 0 &&
                    p->training == pd->training && p->partial_rows <= 0,
                "bn_bwd_pair: the two BatchNorms must share M, C and mode (bf16)");
-    const long long M = p->M;
-    const int C = p->C;
-    const ColGeom g = col_geom(M, C, 8);
-    const long long need = ((long long)g.gy * C * 2 + 4ll * C) * 4;
-    HS_REQUIRE(p->ws && pd->ws && p->ws_bytes >= need && pd->ws_bytes >= need, "bn_bwd_pair: workspace too small");
-    float* coef = (float*)p->ws + (long long)g.gy * C * 2;
-    float* coef_d = (float*)pd->ws + (long long)g.gy * C * 2;
-    hipLaunchKernelGGL(bn_bwd_partial_pair_kernel, dim3(g.gx, g.gy), dim3(256), 0, s, (const bf16_t*)p->dy, (const bf16_t*)p->y,
-                       (const bf16_t*)p->x, p->save_mean, p->save_invstd, (const bf16_t*)pd->x, pd->save_mean, pd->save_invstd, M, C,
-                       g.tpc, (float*)p->ws, (float*)pd->ws);
-    HS_LAUNCH_CHECK();
-    const BnFinalSet fa = {(const float*)p->ws, p->gamma, p->save_mean, p->save_invstd, p->dbeta, p->dgamma, coef};
-    const BnFinalSet fb = {(const float*)pd->ws, pd->gamma, pd->save_mean, pd->save_invstd, pd->dbeta, pd->dgamma, coef_d};
-    hipLaunchKernelGGL(bn_bwd_final_pair_kernel, dim3(ceil_div(C, 4), 2), dim3(256), 0, s, fa, fb, g.gy, C, 1.f / (float)M,
-                       p->training);
-    HS_LAUNCH_CHECK();
-    const long long nch = M * C / 8;
-    const int blocks = (int)std::min<long long>((nch + 255) / 256, 4096);
-    hipLaunchKernelGGL(bn_bwd_apply_pair_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)p->dy, (const bf16_t*)p->y,
-                       (const bf16_t*)p->x, coef, (const bf16_t*)pd->x, coef_d, (bf16_t*)p->dx, (bf16_t*)pd->dx, nch, C / 8, C);
-    HS_LAUNCH_CHECK();
-    return HS_OK;
+    return bn_bwd_run<bf16_t, GradStored, true>("bn_bwd_pair", p, pd, p->y, GradStored{}, s);
 }
 long long bn_ws_bytes(long long M, int C, int dtype) {
     ColGeom g = col_geom(M, C, dtype == HS_BF16 ? 8 : 4);
@@ -949,7 +743,7 @@ long long bn_ws_bytes(long long M, int C, int dtype) {
     // (+ the merge rows of a GEMM that also finishes the statistics: one per 32 tile rows, hs_gemm_bn_finish_rows)
     const long long tiles = (M + 63) / 64;
     const long long rows = std::max<long long>(g.gy, tiles + (tiles + 31) / 32);
-    return rows * C * 3 * 4 + 4ll * C * 4;
+    return rows * C * 3 * 4 + bn_bwd_ws_bytes(0, C);
 }
 
 // ============================================================================================
