@@ -1033,6 +1033,36 @@ hs_status hs_gradcam(int32_t dtype, const void* act, const void* grad, float* ca
 hs_status hs_stage_images_u8(const uint8_t* src, float* out, int32_t B, int32_t H, int32_t W, const float* mean,
                              const float* std, void* stream);
 
+/* Device-side augmentation: the loaders' PIL transforms (RandomResizedCrop, flips, RandomRotation, ColorJitter; Resize +
+   CenterCrop for eval) from a pack of decoded u8 images to the f32 [N][3][S][S] batch, bit-equal to Pillow's arithmetic
+   (tests/augment_ref.py restates it).  The pack: one device byte arena; source i is [h][w][3] u8, tightly packed, at byte
+   src_off[i] (any alignment).  All tables are HOST arrays, checked before any launch; only `arena`, `ws` and `out` are device
+   memory.  Per output n:
+     iparams[n][16] = source index, crop box top, left, h, w, hflip, vflip, rotate (0: no rotation stage), the colour order as a
+                      permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue (4 ints), enable[op] (4 ints, by op)
+     fparams[n][5]  = angle in degrees (Image.rotate's sign), brightness, contrast, saturation factors, hue shift in [-0.5, 0.5]
+   Passes, in stream order, all on one workspace of hs_augment_ws_bytes (16-byte aligned):
+     plan    resampling windows + 22-bit coefficients per output and axis, rotation matrices in 16.16, the output records
+     resize  crop box -> S x S u8: horizontal pass (rounded to u8, rows the vertical pass reads), then the vertical pass
+     stats   per output, the integer sum of L of the image as its contrast op meets it (skippable when no output has contrast)
+     finish  rotation / flip gather (fill 0), colour ops in order with the u8 store between them, (v/255 - mean[c]) / std[c]
+   The eval plan is Resize(R) + CenterCrop(S) of whole sources: shorter side to R, longer to int(R * long / short), window at
+   int(round((len - S) / 2.0)) (half to even); R >= S.  The ws queries return -1 on a bad argument. */
+int64_t hs_augment_ws_bytes(const int32_t* iparams, int32_t N, int32_t S);
+int64_t hs_augment_eval_ws_bytes(const int32_t* src_h, const int32_t* src_w, int32_t n_src, const int32_t* src_index, int32_t N,
+                                 int32_t R, int32_t S);
+/* byte offset inside the workspace of what == 0: the int64 L sums [N] (stats), what == 1: the resized u8 images [N][S][S][3] */
+int64_t hs_augment_ws_offset(int32_t what, int32_t N, int32_t S);
+hs_status hs_augment_plan(const int32_t* src_h, const int32_t* src_w, const int64_t* src_off, int32_t n_src, int64_t arena_bytes,
+                          const int32_t* iparams, const double* fparams, int32_t N, int32_t S, void* ws, int64_t ws_bytes,
+                          void* stream);
+hs_status hs_augment_plan_eval(const int32_t* src_h, const int32_t* src_w, const int64_t* src_off, int32_t n_src,
+                               int64_t arena_bytes, const int32_t* src_index, int32_t N, int32_t R, int32_t S, void* ws,
+                               int64_t ws_bytes, void* stream);
+hs_status hs_augment_resize(const uint8_t* arena, void* ws, int32_t N, int32_t S, void* stream);
+hs_status hs_augment_stats(void* ws, int32_t N, int32_t S, void* stream);
+hs_status hs_augment_finish(const void* ws, float* out, int32_t N, int32_t S, const float* mean, const float* std, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
