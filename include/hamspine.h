@@ -1063,6 +1063,43 @@ hs_status hs_augment_resize(const uint8_t* arena, void* ws, int32_t N, int32_t S
 hs_status hs_augment_stats(void* ws, int32_t N, int32_t S, void* stream);
 hs_status hs_augment_finish(const void* ws, float* out, int32_t N, int32_t S, const float* mean, const float* std, void* stream);
 
+/* Device-side validation metrics (csrc/metrics.hip): the multiclass confusion matrix, precision / recall / F1 / accuracy and
+   one-vs-rest AUROC without a host round trip per batch.  State lives in caller-owned device tensors:
+     cm       [C][C] int64, row = label, column = prediction        invalid  one int64: rows whose label is outside [0, C)
+     scores   [C][capacity] f32, class-major                        labels   [capacity] int32, -1 for an invalid row
+   The number of stored rows n is a host integer.  2 <= C <= HS_METRICS_MAX_CLASSES; capacity < 2^31. */
+#define HS_METRICS_MAX_CLASSES 64
+/* the f64 vector of hs_metrics_finalize: HS_METRICS_SCALARS averages -- accuracy, macro precision / recall / F1, support-weighted
+   precision / recall / F1, macro AUROC -- then HS_METRICS_PER_CLASS arrays of C: precision, recall, F1, AUROC, support */
+#define HS_METRICS_SCALARS 8
+#define HS_METRICS_PER_CLASS 5
+/* One validation batch: logits [B][C] f32 or bf16, labels [B] int64, stored as rows n .. n + B - 1.  Per row: arg-max (lowest
+   index on ties; NaN counts as the largest value, as in torch.argmax), softmax in f32 with the maximum subtracted (from_logits
+   == 0 stores the values as given), the C scores written to column n + row, the label stored, cm[label][argmax] += 1.  A label
+   outside [0, C) adds one to `invalid` instead; its score column is NaN and its stored label -1.  scores == labels == NULL
+   keeps the matrix alone.  Replaces torch.argmax + MetricCollection.update + AUROC.update of reference
+   ConNexT/models/pl_model_MOE2.py:159-163 and the per-batch .cpu() of scripts/train.py:113-119, mibf_net/train_resnet.py:52-57,
+   ConNexT/models/test.py:97-104. */
+hs_status hs_metrics_update(int32_t dtype, const void* logits, const int64_t* labels, int32_t B, int32_t C, int64_t n,
+                            int64_t capacity, int64_t* cm, int64_t* invalid, float* scores, int32_t* stored_labels,
+                            int32_t from_logits, void* stream);
+/* cm[labels[i]][preds[i]] += 1 for i < B; a label or prediction outside [0, C) adds one to `invalid` instead.
+   Replaces MetricCollection.update(pred_labels, labels) (pl_model_MOE2.py:161,163). */
+hs_status hs_metrics_update_preds(const int64_t* preds, const int64_t* labels, int64_t B, int32_t C, int64_t* cm,
+                                  int64_t* invalid, void* stream);
+/* counts [C][4] int64, overwritten: per class c over the n stored rows, with positives = rows labelled c and negatives = rows
+   with any other valid label: the number of (positive i, negative j) pairs with s_j < s_i, the number with s_j == s_i, the number
+   of positives, the number of negatives.  Replaces torchmetrics AUROC.compute (pl_model_MOE2.py:170) and
+   sklearn.metrics.roc_auc_score on host copies (mibf_net/predict_resnet_ham_image.py:103-110). */
+hs_status hs_metrics_auroc(const float* scores, const int32_t* labels, int64_t n, int64_t capacity, int32_t C, int64_t* counts,
+                           void* stream);
+/* out: HS_METRICS_SCALARS + HS_METRICS_PER_CLASS * C doubles, laid out as above; every division in f64 from the integer counts,
+   0 where a denominator is 0.  Macro averages run over the classes with tp + fp + fn > 0, the weighted ones use the supports.
+   AUROC of a class is (2 less + eq) / (2 P Nn), NaN without a positive or without a negative; its macro average runs over the
+   defined classes.  counts == NULL: every AUROC is NaN.  Replaces the torchmetrics .compute() calls of pl_model_MOE2.py:169-171
+   and the sklearn calls of ConNexT/models/test.py:112-130, scripts/train.py:121-129. */
+hs_status hs_metrics_finalize(const int64_t* cm, const int64_t* counts, int32_t C, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

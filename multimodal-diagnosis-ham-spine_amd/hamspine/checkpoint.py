@@ -6,7 +6,8 @@ files move between the two code bases in both directions.  This module restates 
 drivers wrap around that:
 
 * `load_checkpoint`  - tolerant loader of reference mibf_net/predict_resnet.py:13-23 (`{"state_dict": ...}` wrapper,
-  `module.` prefixes left by DataParallel / DDP, non-strict with a report of what did not match);
+  `module.` prefixes left by DataParallel / DDP, non-strict with a report of what did not match); a Lightning `.ckpt`
+  (`state_dict` beside `hyper_parameters`, `epoch`, `global_step`, as `hamspine.lightning_shim` writes it) is such a wrapper;
 * `TopKCheckpoints`  - the "keep the 3 best epochs" policy of reference scripts/train.py:411-428 (same file names,
   strict `>` against the current worst, the evicted file is deleted, DataParallel / DDP wrappers are unwrapped).
 

@@ -296,3 +296,8 @@ class ConvNextFeatures(nn.Sequential):
 def convnext_base_features(stochastic_depth_prob=0.5):
     """torchvision.models.convnext_base(weights=None).features (stochastic depth 0.5, layer scale 1e-6)."""
     return ConvNextFeatures([128, 256, 512, 1024], [3, 3, 27, 3], stochastic_depth_prob)
+
+
+def convnext_large_features(stochastic_depth_prob=0.5):
+    """torchvision.models.convnext_large(weights=None).features (reference ConNexT/models/pl_model_MOE2.py:39-43)."""
+    return ConvNextFeatures([192, 384, 768, 1536], [3, 3, 27, 3], stochastic_depth_prob)
