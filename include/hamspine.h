@@ -394,6 +394,27 @@ hs_status hs_adam_step_multi_shadow(int32_t count, float* const* params, const f
    not overlap until _end returns.  No reference counterpart (cuBLAS launches every GEMM on its own). */
 hs_status hs_wgrad_group_begin(void* stream);
 hs_status hs_wgrad_group_end(void* stream);
+/* Deferred weight-gradient set.  While a set is open on `stream`, hs_linear_bwd launches only its data-gradient GEMM there and
+   hands the row-major ("tn") weight gradient and the bias gradient to the set, copied by value (x, dy, leading dimensions, M,
+   in_f, out_f, dtype, dw, db).  _flush launches them: the bf16 weight gradients as ONE grouped grid (per problem the tile, the
+   split of hs_gemm_suggest_split and the reduction order of its own launch: the same bits), f32 ones one by one, and all bias
+   gradients as ONE column-sum partial launch and ONE final launch (per problem the chunking and order of hs_colsum), then
+   closes the set.  The caller keeps every x, dy, dw, db alive and unchanged until _flush has returned; ws holds
+   hs_wgrad_defer_ws_bytes(stream) bytes (asked right before the flush).  A set holds up to 64 problems; a full set, the
+   K-contiguous form (with its hs_wgrad_group_* scope) and the HAMSPINE_OVERLAP=1 mode take the immediate path.  _begin on an
+   open set keeps it; _suspend leaves the set open but sends hs_linear_bwd down the immediate path until the next _begin (a
+   caller brackets the calls whose operands it keeps alive with _begin / _suspend, so that other callers on the stream never feed
+   the set); _abort drops a set without launching; _open / _pending: 1 / the number of problems held, 0 with no set.
+   _counters: out[5] = problems deferred, problems flushed, grouped launches, column-sum launches, table uploads (process
+   totals).  No reference counterpart (autograd runs every gradient where its node is). */
+hs_status hs_wgrad_defer_begin(void* stream);
+hs_status hs_wgrad_defer_suspend(void* stream);
+int32_t hs_wgrad_defer_open(void* stream);
+int32_t hs_wgrad_defer_pending(void* stream);
+int64_t hs_wgrad_defer_ws_bytes(void* stream);
+hs_status hs_wgrad_defer_flush(void* stream, void* ws, int64_t ws_bytes);
+hs_status hs_wgrad_defer_abort(void* stream);
+void hs_wgrad_defer_counters(int64_t* out);
 /* bf16 shadow registry: while registered, every composite / tower reads `bf16` (n elements of the weight, same memory order)
    instead of casting `w` in its forward.  The caller keeps it equal to bf16(w).  bf16 = NULL forgets the entry.  No
    reference counterpart (torch autocast re-casts weights per call). */

@@ -4,6 +4,7 @@
 // (scratch).  The same layout code runs in "plan" mode (no launches) to answer the *_query calls, so
 // sizes and pointers cannot drift apart.
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -43,6 +44,11 @@ GemmGroup* gemm_group_open(hipStream_t s, long long slot);   // slot: any key th
 int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s, const int* k_cols = nullptr);
 bool gemm_group_takes_k_cols();
 int gemm_group_flush(GemmGroup* g, hipStream_t s);
+void gemm_group_upload_on_stream(GemmGroup* g);       // a changed problem table travels on the stream, no synchronise
+long long gemm_group_uploads(const GemmGroup* g);
+long long gemm_group_launches(const GemmGroup* g);
+int colsum_multi(int count, const int* dtype, const void* const* x, const long long* M, const int* N, const int* ld, float* const* out,
+                 float* const* ws, hipStream_t s, int* launches);
 bool fused_attention_enabled();
 int attention_bwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, const void* dO, void* dq, void* dk,
                         void* dv, const void* P, int ldP, void* scratch, long long scratch_bytes, const void* O, hipStream_t s,
@@ -523,18 +529,69 @@ static GemmGroup* open_wgrad_group(hipStream_t s) {
     auto it = g_wg_open.find(s);
     return it == g_wg_open.end() ? nullptr : it->second;
 }
+// Deferred weight-gradient set (hs_wgrad_defer_begin / _flush): while a set is open on a stream, hs_linear_bwd launches only
+// its data-gradient GEMM and leaves the row-major ("tn") weight gradient and the bias gradient here, BY VALUE.  The flush runs
+// the bf16 weight gradients as one grouped grid (the 64x64 split-K body the ResNet tower's pointwise weight gradients share: per
+// problem the tile, the split of hs_gemm_suggest_split, the slabs and the in-launch reduction of its own launch, so the same
+// bits) and the bias gradients as one multi-problem column-sum pair.  A backward's serial chain of small Linear layers (fusion
+// block, head) then consists of its data-gradient GEMMs alone; nothing but the optimizer reads these gradients.  The caller
+// keeps x, dy, dw, db alive and unchanged until the flush has been enqueued.
+constexpr int kWgradDeferMax = 64;           // the grouped grid's problem table, and the column-sum table
+struct DeferredWgrad {
+    int dtype;
+    const void *x, *dy;
+    long long M;
+    int ldx, ldy, in_f, out_f;
+    float *dw, *db;
+};
+static std::mutex g_wd_mu;
+static std::unordered_map<hipStream_t, std::vector<DeferredWgrad>> g_wd_open;
+static std::unordered_map<hipStream_t, bool> g_wd_suspended;     // open, but hs_linear_bwd takes the immediate path (hs_wgrad_defer_suspend)
+static std::atomic<long long> g_wd_deferred{0}, g_wd_flushed{0}, g_wd_grouped{0}, g_wd_colsum{0}, g_wd_uploads{0};
+static bool wgrad_defer_has_room(hipStream_t s) {
+    std::lock_guard<std::mutex> lk(g_wd_mu);
+    auto it = g_wd_open.find(s);
+    return it != g_wd_open.end() && (int)it->second.size() < kWgradDeferMax && !g_wd_suspended.count(s);
+}
+static void wgrad_defer_push(hipStream_t s, int dtype, const void* x, long long M, int ldx, const hs_linear& lin, const void* dy, int ldy) {
+    std::lock_guard<std::mutex> lk(g_wd_mu);
+    auto it = g_wd_open.find(s);
+    if (it == g_wd_open.end()) return;
+    it->second.push_back(DeferredWgrad{dtype, x, dy, M, ldx, ldy, lin.in_f, lin.out_f, lin.dw, lin.db});
+    g_wd_deferred.fetch_add(1, std::memory_order_relaxed);
+}
 static bool wgrad_nt_enabled();
 static int linear_wgrad_nt_run(Run& r, const void* xT, const void* dyT, long long M, int in_f, int out_f, float* dw, float* db,
                                int seg_rows, float* const* dw_seg, float* const* db_seg, const int* k_cols = nullptr);
+// bf16, compute-bound shapes (in*out/(in+out) FLOP per operand byte above the ridge; ConvNeXt's 512 <-> 2048 MLPs over
+// 12544 tokens: 172 us as a "tn" GEMM with transposed LDS reads): transpose dY and X once (one launch) and run the
+// K-contiguous GEMM, as the BertLayer backward does.  Long-K / small-output shapes stay on the split-K "tn" form (they are
+// HBM-bound and the transposes would double their traffic).
+static bool linear_wgrad_takes_nt(int dt, long long M, int ldx, const hs_linear& lin, int ldy) {
+    return lin.dw && dt == HS_BF16 && wgrad_nt_enabled() && M >= 2048 && M % 8 == 0 && lin.in_f % 8 == 0 && lin.out_f % 8 == 0 &&
+           ldx % 8 == 0 && ldy % 8 == 0 && ldx >= lin.in_f && ldy >= lin.out_f &&
+           (long long)lin.in_f * lin.out_f >= 256ll * (lin.in_f + lin.out_f);
+}
+// the row-major ("tn") weight-gradient GEMM dw = dy^T x; *db_done: the launch also writes the bias gradient
+static hs_gemm_params linear_wgrad_tn_params(int dt, const void* x, long long M, int ldx, const hs_linear& lin, const void* dy, int ldy,
+                                             bool* db_done) {
+    hs_gemm_params p = gemm_defaults(dt);
+    p.a_kind = HS_A_RC; p.b_kind = HS_B_RC;
+    p.M = lin.out_f; p.N = lin.in_f; p.K = (int)M;
+    p.A = dy; p.B = x;
+    p.a_elems = (M - 1) * ldy + lin.out_f;
+    p.b_elems = (M - 1) * ldx + lin.in_f;
+    p.lda = ldy; p.ldb = ldx;
+    p.D = lin.dw; p.ldd = lin.in_f; p.out_dtype = HS_F32;
+    if (lin.db && bias_in_wgrad(dt, lin.out_f, lin.in_f, M)) {
+        p.rowsum_a = lin.db;
+        *db_done = true;
+    }
+    return p;
+}
 static int linear_wgrad_run(Run& r, const void* x, long long M, int ldx, const hs_linear& lin, const void* dy, int ldy) {
     bool db_done = false;
-    // bf16, compute-bound shapes (in*out/(in+out) FLOP per operand byte above the ridge; ConvNeXt's 512 <-> 2048 MLPs over
-    // 12544 tokens: 172 us as a "tn" GEMM with transposed LDS reads): transpose dY and X once (one launch) and run the
-    // K-contiguous GEMM, as the BertLayer backward does.  Long-K / small-output shapes stay on the split-K "tn" form (they are
-    // HBM-bound and the transposes would double their traffic).
-    if (lin.dw && r.dt == HS_BF16 && wgrad_nt_enabled() && M >= 2048 && M % 8 == 0 && lin.in_f % 8 == 0 && lin.out_f % 8 == 0 &&
-        ldx % 8 == 0 && ldy % 8 == 0 && ldx >= lin.in_f && ldy >= lin.out_f &&
-        (long long)lin.in_f * lin.out_f >= 256ll * (lin.in_f + lin.out_f)) {
+    if (linear_wgrad_takes_nt(r.dt, M, ldx, lin, ldy)) {
         const long long mk = r.ws.mark();
         char* tA = (char*)r.ws.alloc(M * (long long)lin.out_f * 2);
         char* tB = (char*)r.ws.alloc(M * (long long)lin.in_f * 2);
@@ -568,18 +625,7 @@ static int linear_wgrad_run(Run& r, const void* x, long long M, int ldx, const h
     }
     if (lin.dw) {
         HS_REQUIRE(!r.pk_T, "linear_wgrad: packed rows need the transposed-operand weight gradients (HAMSPINE_WGRAD_NT)");
-        hs_gemm_params p = gemm_defaults(r.dt);
-        p.a_kind = HS_A_RC; p.b_kind = HS_B_RC;
-        p.M = lin.out_f; p.N = lin.in_f; p.K = (int)M;
-        p.A = dy; p.B = x;
-        p.a_elems = (M - 1) * ldy + lin.out_f;
-        p.b_elems = (M - 1) * ldx + lin.in_f;
-        p.lda = ldy; p.ldb = ldx;
-        p.D = lin.dw; p.ldd = lin.in_f; p.out_dtype = HS_F32;
-        if (lin.db && bias_in_wgrad(r.dt, lin.out_f, lin.in_f, M)) {
-            p.rowsum_a = lin.db;
-            db_done = true;
-        }
+        hs_gemm_params p = linear_wgrad_tn_params(r.dt, x, M, ldx, lin, dy, ldy, &db_done);
         HS_PROPAGATE(gemm_splitk(r, p));
     }
     if (lin.db && !db_done) {
@@ -589,6 +635,56 @@ static int linear_wgrad_run(Run& r, const void* x, long long M, int ldx, const h
         CALL(r, colsum_rows(r.dt, dy, M, lin.out_f, ldy, lin.db, w, wsb, 0, r.pk_inv, r.s));
         if (r.plan ? !overlap_enabled() : !r.side) r.ws.release(mk);
     }
+    return HS_OK;
+}
+// ---- deferred weight-gradient set (hs_wgrad_defer_*) --------------------------------------------------------------------
+static int wgrad_defer_run(Run& r, const std::vector<DeferredWgrad>& items, long long* grouped_launches, long long* colsum_launches,
+                           long long* uploads) {
+    GemmGroup* g = nullptr;
+    if (!r.plan) {
+        g = gemm_group_open(r.s, -2);
+        HS_REQUIRE(g != nullptr, "wgrad_defer_flush: cannot set up the group");
+        gemm_group_upload_on_stream(g);
+    }
+    const long long l0 = gemm_group_launches(g), u0 = gemm_group_uploads(g);
+    r.grp_pw = g;
+    int nb = 0;
+    int b_dt[kWgradDeferMax], b_N[kWgradDeferMax], b_ld[kWgradDeferMax];
+    const void* b_x[kWgradDeferMax];
+    long long b_M[kWgradDeferMax];
+    float *b_out[kWgradDeferMax], *b_ws[kWgradDeferMax];
+    for (const DeferredWgrad& it : items) {
+        hs_linear lin;
+        memset(&lin, 0, sizeof(lin));
+        lin.in_f = it.in_f; lin.out_f = it.out_f; lin.dw = it.dw; lin.db = it.db;
+        bool db_done = false;
+        r.dt = it.dtype;
+        if (it.dw) {
+            hs_gemm_params p = linear_wgrad_tn_params(it.dtype, it.x, it.M, it.ldx, lin, it.dy, it.ldy, &db_done);
+            // bf16: queued for the grouped grid with the split, the tile and the slabs its own launch would have (the slabs stay
+            // allocated until the grid has run); what the grid cannot take, and f32, is launched here as before
+            r.defer_wgrad = it.dtype == HS_BF16;
+            HS_PROPAGATE(gemm_splitk(r, p, true));
+        }
+        if (it.db && !db_done) {
+            b_dt[nb] = it.dtype; b_x[nb] = it.dy; b_M[nb] = it.M; b_N[nb] = it.out_f; b_ld[nb] = it.ldy; b_out[nb] = it.db;
+            b_ws[nb] = (float*)r.ws.alloc(hs_colsum_ws_bytes(it.M, it.out_f));
+            ++nb;
+        }
+    }
+    if (r.plan) return HS_OK;
+    if (r.ws.overflow) {
+        set_error("wgrad_defer_flush: workspace too small (%lld needed, %lld given)", r.ws.peak, r.ws.cap);
+        return HS_ERR_ARG;
+    }
+    HS_PROPAGATE(gemm_group_flush(g, r.s));
+    if (nb > 0) {
+        int made = 0;
+        HS_PROPAGATE(colsum_multi(nb, b_dt, b_x, b_M, b_N, b_ld, b_out, b_ws, r.s, &made));
+        *colsum_launches += made;
+    }
+    *grouped_launches += gemm_group_launches(g) - l0;
+    *uploads += gemm_group_uploads(g) - u0;
     return HS_OK;
 }
 // The same gradients from TRANSPOSED operands (bf16): dyT [out][M] and xT [in][M] are both K-contiguous along the token
@@ -2350,8 +2446,12 @@ hs_status hs_linear_bwd(int32_t dtype, const void* x, int64_t M, int32_t ldx, co
                         void* stream) {
     HS_REQUIRE(x && lin && dy && lin->w, "linear_bwd: null argument");
     HS_REQUIRE(dtype == HS_F32 || w_lp || !dx, "linear_bwd: bf16 mode needs the bf16 weight copy");
+    // an open deferred set on this stream (hs_wgrad_defer_begin) takes the row-major weight / bias gradient: only the data
+    // gradient is launched here
+    const bool deferred = (lin->dw || lin->db) && !overlap_enabled() && !linear_wgrad_takes_nt(dtype, M, ldx, *lin, ldy) &&
+                          wgrad_defer_has_room((hipStream_t)stream);
     auto both = [&](Run& r) -> int {
-        HS_PROPAGATE(linear_wgrad_run(r, x, M, ldx, *lin, dy, ldy));
+        if (!deferred) HS_PROPAGATE(linear_wgrad_run(r, x, M, ldx, *lin, dy, ldy));
         if (dx)
             HS_PROPAGATE(linear_dgrad_run(r, *lin, dtype == HS_F32 ? (const void*)lin->w : w_lp, dy, M, ldy, dx, lddx, dx_dtype,
                                           mul_mode, mul_src, ldm, dx_residual));
@@ -2362,7 +2462,79 @@ hs_status hs_linear_bwd(int32_t dtype, const void* x, int64_t M, int32_t ldx, co
     run_init(r, dtype, false, nullptr, 0, ws, ws_bytes, (hipStream_t)stream);
     HS_PROPAGATE(both(r));
     RUN_CHECK_ARENAS(r, "linear_bwd");
+    if (deferred) wgrad_defer_push((hipStream_t)stream, dtype, x, M, ldx, *lin, dy, ldy);
     return HS_OK;
+}
+
+/* deferred weight-gradient set: see wgrad_defer_run */
+hs_status hs_wgrad_defer_begin(void* stream) {
+    std::lock_guard<std::mutex> lk(g_wd_mu);
+    g_wd_open[(hipStream_t)stream];          // opens an empty set, or keeps the open one
+    g_wd_suspended.erase((hipStream_t)stream);
+    return HS_OK;
+}
+hs_status hs_wgrad_defer_suspend(void* stream) {
+    std::lock_guard<std::mutex> lk(g_wd_mu);
+    if (g_wd_open.count((hipStream_t)stream)) g_wd_suspended[(hipStream_t)stream] = true;
+    return HS_OK;
+}
+int32_t hs_wgrad_defer_open(void* stream) {
+    std::lock_guard<std::mutex> lk(g_wd_mu);
+    return g_wd_open.count((hipStream_t)stream) ? 1 : 0;
+}
+int32_t hs_wgrad_defer_pending(void* stream) {
+    std::lock_guard<std::mutex> lk(g_wd_mu);
+    auto it = g_wd_open.find((hipStream_t)stream);
+    return it == g_wd_open.end() ? 0 : (int32_t)it->second.size();
+}
+int64_t hs_wgrad_defer_ws_bytes(void* stream) {
+    std::vector<DeferredWgrad> items;
+    {
+        std::lock_guard<std::mutex> lk(g_wd_mu);
+        auto it = g_wd_open.find((hipStream_t)stream);
+        if (it != g_wd_open.end()) items = it->second;
+    }
+    Run r;
+    run_init(r, HS_BF16, true, nullptr, 0, nullptr, 0, nullptr);
+    long long a = 0, b = 0, c = 0;
+    if (wgrad_defer_run(r, items, &a, &b, &c) != HS_OK) return -1;
+    return r.ws.peak + 1024;
+}
+hs_status hs_wgrad_defer_flush(void* stream, void* ws, int64_t ws_bytes) {
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<DeferredWgrad> items;
+    {
+        std::lock_guard<std::mutex> lk(g_wd_mu);
+        auto it = g_wd_open.find(s);
+        if (it == g_wd_open.end()) return HS_OK;
+        items.swap(it->second);
+        g_wd_open.erase(it);                 // closed whatever happens below: an error leaves no set behind
+        g_wd_suspended.erase(s);
+    }
+    if (items.empty()) return HS_OK;
+    HS_REQUIRE(ws != nullptr, "wgrad_defer_flush: null workspace");
+    Run r;
+    run_init(r, HS_BF16, false, nullptr, 0, ws, ws_bytes, s);
+    long long gl = 0, cl = 0, up = 0;
+    const int st = wgrad_defer_run(r, items, &gl, &cl, &up);
+    if (st == HS_OK) g_wd_flushed.fetch_add((long long)items.size(), std::memory_order_relaxed);
+    g_wd_grouped.fetch_add(gl, std::memory_order_relaxed);
+    g_wd_colsum.fetch_add(cl, std::memory_order_relaxed);
+    g_wd_uploads.fetch_add(up, std::memory_order_relaxed);
+    return st;
+}
+hs_status hs_wgrad_defer_abort(void* stream) {
+    std::lock_guard<std::mutex> lk(g_wd_mu);
+    g_wd_open.erase((hipStream_t)stream);
+    g_wd_suspended.erase((hipStream_t)stream);
+    return HS_OK;
+}
+void hs_wgrad_defer_counters(int64_t* out) {
+    out[0] = g_wd_deferred.load(std::memory_order_relaxed);
+    out[1] = g_wd_flushed.load(std::memory_order_relaxed);
+    out[2] = g_wd_grouped.load(std::memory_order_relaxed);
+    out[3] = g_wd_colsum.load(std::memory_order_relaxed);
+    out[4] = g_wd_uploads.load(std::memory_order_relaxed);
 }
 int64_t hs_linear_bwd_ws_bytes(int64_t M, int32_t in_f, int32_t out_f, int32_t dtype) {
     // a plan-mode pass of the code hs_linear_bwd runs (split-K slabs incl. group slabs, column-sum partials, the transposed

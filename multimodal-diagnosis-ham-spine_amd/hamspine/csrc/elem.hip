@@ -342,17 +342,19 @@ __global__ __launch_bounds__(256) void mul_dev_scalar_kernel(const float* __rest
 // ============================================================================================
 // column sum: X [M][N] -> out[N] (f32), used for bias gradients.  Deterministic two-stage.
 // ============================================================================================
+// (bx, by, gy: the block's place in the single-problem grid and that grid's y extent -- blockIdx / gridDim in the kernels right
+// below, worked out from the problem table in colsum_multi_partial_kernel: one body, so the sums are the same bits either way)
 template <typename T>
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict__ x, long long M_pad, int N, int ld,
-                                                             float* __restrict__ ws, const int* __restrict__ inv) {
-    // thread per column, blockIdx.y strides rows (generic, works for any N / ld)
+__device__ __forceinline__ void colsum_partial_body(const T* __restrict__ x, long long M_pad, int N, int ld, float* __restrict__ ws,
+                                                    const int* __restrict__ inv, int bx, int by, int gy) {
+    // thread per column, by strides rows (generic, works for any N / ld)
     // inv (packed rows): the walk is over PADDED rows, row r read from packed row inv[r] and left out where inv[r] < 0 -- the
     // padded tower adds an exact zero there, so the sums are its sums, term by term in the same order
     const long long M = M_pad;
-    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int c = bx * 256 + threadIdx.x;
     if (c >= N) return;
     float acc = 0.f;
-    for (long long r = blockIdx.y; r < M; r += gridDim.y) {
+    for (long long r = by; r < M; r += gy) {
         long long sr = r;
         if (inv) {
             sr = inv[r];
@@ -360,27 +362,32 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict
         }
         acc += to_f32(x[sr * ld + c]);
     }
-    ws[(long long)blockIdx.y * N + c] = acc;
+    ws[(long long)by * N + c] = acc;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict__ x, long long M_pad, int N, int ld,
+                                                             float* __restrict__ ws, const int* __restrict__ inv) {
+    colsum_partial_body<T>(x, M_pad, N, ld, ws, inv, blockIdx.x, blockIdx.y, gridDim.y);
 }
 // 16-byte variant (N, ld multiples of the chunk, base aligned): a block covers min(64, N / chunk) chunk columns and
 // 256 / that many rows per pass (narrow matrices -- ConvNeXt's 200704 x 128 -- used to leave 3/4 of a 64-column block idle:
 // 155 us); the row lanes merge through LDS in a fixed order
 template <typename T>
-__global__ __launch_bounds__(256) void colsum_partial_vec_kernel(const T* __restrict__ x, long long M_pad, int N, int ld,
-                                                                 float* __restrict__ ws, const int* __restrict__ inv) {
+__device__ __forceinline__ void colsum_partial_vec_body(const T* __restrict__ x, long long M_pad, int N, int ld,
+                                                        float* __restrict__ ws, const int* __restrict__ inv,
+                                                        float (*sh)[Chunk<T>::N], int bx, int by, int gy) {
     constexpr int E = Chunk<T>::N;
-    const long long M = M_pad;                       // inv: as in colsum_partial_kernel
-    __shared__ float sh[256][E];
-    const int ncol = min(64, N / E - (int)blockIdx.x * 64);     // chunk columns of this block
+    const long long M = M_pad;                       // inv: as in colsum_partial_body
+    const int ncol = min(64, N / E - bx * 64);                  // chunk columns of this block
     const int rpb = 256 / ncol;                                 // rows per pass
     const int tid = threadIdx.x;
     const int ty = tid / ncol, tx = tid - ty * ncol;
-    const int cc = blockIdx.x * 64 + tx;
+    const int cc = bx * 64 + tx;
     float acc[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) acc[e] = 0.f;
     if (ty < rpb) {
-        for (long long r = (long long)blockIdx.y * rpb + ty; r < M; r += (long long)gridDim.y * rpb) {
+        for (long long r = (long long)by * rpb + ty; r < M; r += (long long)gy * rpb) {
             long long sr = r;
             if (inv) {
                 sr = inv[r];
@@ -400,15 +407,20 @@ __global__ __launch_bounds__(256) void colsum_partial_vec_kernel(const T* __rest
         for (int e = 0; e < E; ++e) {
             float t = 0.f;
             for (int r = 0; r < rpb; ++r) t += sh[r * ncol + tx][e];
-            ws[(long long)blockIdx.y * N + cc * E + e] = t;
+            ws[(long long)by * N + cc * E + e] = t;
         }
     }
 }
-__global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restrict__ ws, int gy, int N,
-                                                           float* __restrict__ out, int accumulate) {
-    __shared__ float sh[4][64];
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_partial_vec_kernel(const T* __restrict__ x, long long M_pad, int N, int ld,
+                                                                 float* __restrict__ ws, const int* __restrict__ inv) {
+    __shared__ float sh[256][Chunk<T>::N];
+    colsum_partial_vec_body<T>(x, M_pad, N, ld, ws, inv, sh, blockIdx.x, blockIdx.y, gridDim.y);
+}
+__device__ __forceinline__ void colsum_final_body(const float* __restrict__ ws, int gy, int N, float* __restrict__ out,
+                                                  int accumulate, float (*sh)[64], int bx) {
     const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
+    const int c = bx * 64 + cl;
     float acc = 0.f;
     if (c < N) {
         int i = rg;
@@ -425,6 +437,55 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
         const float t = (sh[0][cl] + sh[1][cl]) + (sh[2][cl] + sh[3][cl]);
         out[c] = accumulate ? out[c] + t : t;
     }
+}
+__global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restrict__ ws, int gy, int N,
+                                                           float* __restrict__ out, int accumulate) {
+    __shared__ float sh[4][64];
+    colsum_final_body(ws, gy, N, out, accumulate, sh, blockIdx.x);
+}
+// Several column sums in one partial launch and one final launch (the bias gradients a deferred weight-gradient set flushes,
+// blocks.hip): the problem table travels in the kernel arguments, a block looks up its problem and walks the single-problem
+// body with that problem's own grid coordinates -- chunking and addition order per problem are those of colsum_t.
+constexpr int kColsumMulti = 64;
+struct ColsumProb {
+    const void* x;
+    float* ws;            // partial rows [gy][N]; == out when the one row group is the result (gy == 1)
+    float* out;
+    int M, N, ld, gy;
+    int nbx;              // blocks along x of the partial grid
+    int f32_vec;          // bit 0: f32 rows (else bf16); bit 1: the 16-byte body
+};
+struct ColsumTable {
+    int n;
+    int first[kColsumMulti + 1];       // first block of each problem in the launch at hand
+    ColsumProb p[kColsumMulti];
+};
+static_assert(sizeof(ColsumTable) <= 3840, "the column-sum problem table travels in the kernel arguments");
+__device__ __forceinline__ int colsum_multi_find(const ColsumTable& t, int b) {
+    int i = 0;
+    while (i + 1 < t.n && t.first[i + 1] <= b) ++i;
+    return i;
+}
+__global__ __launch_bounds__(256) void colsum_multi_partial_kernel(const ColsumTable t) {
+    __shared__ float sh[256][8];
+    const int i = colsum_multi_find(t, blockIdx.x);
+    const ColsumProb& q = t.p[i];
+    const int b = blockIdx.x - t.first[i];
+    const int by = b / q.nbx, bx = b - by * q.nbx;
+    const bool f32 = q.f32_vec & 1, vec = q.f32_vec & 2;
+    if (f32) {
+        if (vec) colsum_partial_vec_body<float>((const float*)q.x, q.M, q.N, q.ld, q.ws, nullptr, (float(*)[4])sh, bx, by, q.gy);
+        else colsum_partial_body<float>((const float*)q.x, q.M, q.N, q.ld, q.ws, nullptr, bx, by, q.gy);
+    } else {
+        if (vec) colsum_partial_vec_body<bf16_t>((const bf16_t*)q.x, q.M, q.N, q.ld, q.ws, nullptr, sh, bx, by, q.gy);
+        else colsum_partial_body<bf16_t>((const bf16_t*)q.x, q.M, q.N, q.ld, q.ws, nullptr, bx, by, q.gy);
+    }
+}
+__global__ __launch_bounds__(256) void colsum_multi_final_kernel(const ColsumTable t) {
+    __shared__ float sh[4][64];
+    const int i = colsum_multi_find(t, blockIdx.x);
+    const ColsumProb& q = t.p[i];
+    colsum_final_body(q.ws, q.gy, q.N, q.out, 0, sh, blockIdx.x - t.first[i]);
 }
 
 // ============================================================================================
@@ -1311,6 +1372,51 @@ int colsum_rows(int dtype, const void* x, long long M, int N, int ld, float* out
                 const int* inv, hipStream_t s) {
     HS_REQUIRE(x && out && M > 0 && N > 0, "colsum: bad argument");
     return DISPATCH_T(dtype, colsum_t, x, M, N, ld, out, (float*)ws, ws_bytes, accumulate, s, inv);
+}
+// count column sums out[i][N] = sum_m x[i][m * ld + n] in ONE partial launch and (when some problem has more than one row group)
+// ONE final launch (*launches: how many it made).  ws[i] holds hs_colsum_ws_bytes(M[i], N[i]) bytes.  Per problem the grids, the chunking and the order of the
+// additions are those of colsum_rows(.., accumulate = 0, inv = NULL): the results are its results bit for bit.
+int colsum_multi(int count, const int* dtype, const void* const* x, const long long* M, const int* N, const int* ld, float* const* out,
+                 float* const* ws, hipStream_t s, int* launches) {
+    HS_REQUIRE(count > 0 && count <= kColsumMulti, "colsum_multi: 1..%d problems", kColsumMulti);
+    ColsumTable tp, tf;
+    tp.n = count;
+    tf.n = 0;
+    int nb_p = 0, nb_f = 0;
+    for (int i = 0; i < count; ++i) {
+        HS_REQUIRE(x[i] && out[i] && M[i] > 0 && M[i] < 0x7fffffffll && N[i] > 0, "colsum_multi: bad argument");
+        HS_REQUIRE(dtype[i] == HS_F32 || dtype[i] == HS_BF16, "colsum_multi: dtype");
+        const bool f32 = dtype[i] == HS_F32;
+        const int E = f32 ? 4 : 8;
+        const int gy = colsum_gy(M[i], N[i]);
+        const bool direct = gy == 1;
+        HS_REQUIRE(direct || ws[i], "colsum_multi: workspace missing");
+        const bool vec = N[i] % E == 0 && ld[i] % E == 0 && ((((uintptr_t)x[i]) & 15) == 0);
+        ColsumProb q;
+        q.x = x[i]; q.ws = direct ? out[i] : ws[i]; q.out = out[i];
+        q.M = (int)M[i]; q.N = N[i]; q.ld = ld[i]; q.gy = gy;
+        q.nbx = vec ? ceil_div(N[i] / E, 64) : ceil_div(N[i], 256);
+        q.f32_vec = (f32 ? 1 : 0) | (vec ? 2 : 0);
+        tp.p[i] = q;
+        tp.first[i] = nb_p;
+        nb_p += q.nbx * gy;
+        if (!direct) {
+            tf.p[tf.n] = q;
+            tf.first[tf.n] = nb_f;
+            nb_f += ceil_div(N[i], 64);
+            ++tf.n;
+        }
+    }
+    tp.first[count] = nb_p;
+    tf.first[tf.n] = nb_f;
+    hipLaunchKernelGGL(colsum_multi_partial_kernel, dim3(nb_p), dim3(256), 0, s, tp);
+    HS_LAUNCH_CHECK();
+    if (launches) *launches = 1;
+    if (tf.n == 0) return HS_OK;
+    hipLaunchKernelGGL(colsum_multi_final_kernel, dim3(nb_f), dim3(256), 0, s, tf);
+    HS_LAUNCH_CHECK();
+    if (launches) *launches = 2;
+    return HS_OK;
 }
 int dropout_rows(int dtype, const void* x, void* out, long long M, int H, float p, unsigned long long seed, const int* nrows,
                  const int* row_of, hipStream_t s) {

@@ -642,6 +642,17 @@ struct GemmGroup {
     char* dev = nullptr;
     size_t dev_cap = 0;
     std::vector<char> shadow;      // what the device table holds
+    // stream_upload (gemm_group_upload_on_stream): a changed table is copied on the group's stream from a ring of pinned
+    // staging buffers instead of behind a stream synchronise.  The stream orders the copy behind the previous launch that read
+    // the table and in front of the next one; a staging slot is reused only after the copy that read it has finished.  For
+    // groups whose operand addresses come from a caching allocator and may move every step (the deferred head-path set).
+    bool stream_upload = false;
+    static constexpr int kStage = 4;
+    char* stage[kStage] = {};
+    size_t stage_cap[kStage] = {};
+    hipEvent_t stage_ev[kStage] = {};
+    int stage_next = 0;
+    long long uploads = 0, launches = 0;
 };
 static constexpr int kGroupMax = 64;
 GemmGroup* gemm_group_open(hipStream_t s, long long slot) {
@@ -665,6 +676,7 @@ GemmGroup* gemm_group_open(hipStream_t s, long long slot) {
 int gemm_group_flush(GemmGroup* g, hipStream_t s) {
     if (!g || g->items.empty()) return HS_OK;
     const int n = (int)g->items.size();
+    ++g->launches;
     constexpr size_t kHead = 512;                                   // first_wg[0..64] and padding
     const size_t bytes = kHead + (size_t)n * sizeof(GemmArgs);
     if (g->combo == 0 && n <= 4 && g->cfg != CFG_P8_256) {          // small groups of the big-tile kind travel in the kernel arguments
@@ -700,7 +712,8 @@ int gemm_group_flush(GemmGroup* g, hipStream_t s) {
             for (size_t i = 0; i < std::min(host.size(), g->shadow.size()); ++i) diff += host[i] != g->shadow[i];
             fprintf(stderr, "[group] table upload: %d problems, %zu bytes (%zu before), %zu bytes differ\n", n, bytes, g->shadow.size(), diff);
         }
-        HS_CHECK_HIP(hipStreamSynchronize(s));
+        ++g->uploads;
+        if (!g->stream_upload || bytes > g->dev_cap) HS_CHECK_HIP(hipStreamSynchronize(s));
         if (bytes > g->dev_cap) {
             if (g->dev) (void)hipFree(g->dev);
             g->dev = nullptr;
@@ -708,7 +721,24 @@ int gemm_group_flush(GemmGroup* g, hipStream_t s) {
             HS_CHECK_HIP(hipMalloc(&g->dev, bytes * 2));
             g->dev_cap = bytes * 2;
         }
-        HS_CHECK_HIP(hipMemcpy(g->dev, host.data(), bytes, hipMemcpyHostToDevice));
+        if (g->stream_upload) {
+            const int k = g->stage_next;
+            g->stage_next = (k + 1) % GemmGroup::kStage;
+            if (g->stage_ev[k]) HS_CHECK_HIP(hipEventSynchronize(g->stage_ev[k]));
+            else HS_CHECK_HIP(hipEventCreateWithFlags(&g->stage_ev[k], hipEventDisableTiming));
+            if (bytes > g->stage_cap[k]) {
+                if (g->stage[k]) (void)hipHostFree(g->stage[k]);
+                g->stage[k] = nullptr;
+                g->stage_cap[k] = 0;
+                HS_CHECK_HIP(hipHostMalloc((void**)&g->stage[k], bytes * 2, hipHostMallocDefault));
+                g->stage_cap[k] = bytes * 2;
+            }
+            memcpy(g->stage[k], host.data(), bytes);
+            HS_CHECK_HIP(hipMemcpyAsync(g->dev, g->stage[k], bytes, hipMemcpyHostToDevice, s));
+            HS_CHECK_HIP(hipEventRecord(g->stage_ev[k], s));
+        } else {
+            HS_CHECK_HIP(hipMemcpy(g->dev, host.data(), bytes, hipMemcpyHostToDevice));
+        }
         g->shadow.swap(host);
     }
     ProfRec rec;
@@ -734,6 +764,9 @@ int gemm_group_flush(GemmGroup* g, hipStream_t s) {
     g->flops = g->bytes = 0;
     return st;
 }
+void gemm_group_upload_on_stream(GemmGroup* g) { if (g) g->stream_upload = true; }
+long long gemm_group_uploads(const GemmGroup* g) { return g ? g->uploads : 0; }
+long long gemm_group_launches(const GemmGroup* g) { return g ? g->launches : 0; }
 // A caller that defers work a grouped GEMM depends on (the BERT tower's dY^T transposes) registers a hook: it runs before any
 // problem that gemm_group_add launches on its own instead of queueing.
 static thread_local int (*g_group_immediate_hook)(void*) = nullptr;
@@ -770,7 +803,10 @@ int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s, const i
         HS_PROPAGATE(gemm_prepare(p, s, q, CFG_256x128));
     const bool ok = big ? (q.bf16 && (q.cfg == CFG_256x128 || q.cfg == CFG_P8_256) && q.combo == 0 && q.batch == 1 && q.split == 1 && !q.a.stamps && !q.a.colstats)
                         : (q.bf16 && q.cfg == CFG_64x64 && (q.combo == 2 || q.combo == 5) && q.batch == 1 && !q.a.stamps &&
-                           (q.split == 1 || q.a.tickets != nullptr) && !q.a.rowsum[0] && !q.a.colstats);
+                           (q.split == 1 || q.a.tickets != nullptr) && !q.a.colstats &&
+                           // row sums (an unsplit Linear weight gradient's bias gradient): the row-contiguous-A body always has
+                           // the code, the grouped instantiation included; they depend on the tile's coordinates alone
+                           (!q.a.rowsum[0] || (q.combo == 2 && q.split == 1)));
     HS_REQUIRE(!k_cols || ok, "gemm_group_add: a problem with chunk-compacted K columns cannot be queued (gemm_group_takes_k_cols)");
     if (!ok) return launch_ungrouped(p, s);
     const long long ngroups = q.split > 1 ? (q.split + kSplitGroup - 1) / kSplitGroup : 0;

@@ -382,8 +382,11 @@ class LinearFn(Function):
         lin = _lin(in_f, out_f, weight, bias, dw, db)
         wsb = _lib().hs_linear_bwd_ws_bytes(M, in_f, out_f, hdt)
         ws = rt.workspace(wsb, x.device)
-        L.check(_lib().hs_linear_bwd(hdt, rt.p(x), M, in_f, C.byref(lin), rt.p(w_lp), rt.p(g), out_f, rt.p(dx), in_f, hdt,
-                                     L.MUL_NONE, None, 0, None, rt.p(ws), ws.numel(), rt.stream()), "hs_linear_bwd")
+        # the weight / bias gradient waits in the stream's deferred set when nothing reads it before the optimizer (rt)
+        with rt.wgrad_defer_scope((weight, bias)) as defer:
+            L.check(_lib().hs_linear_bwd(hdt, rt.p(x), M, in_f, C.byref(lin), rt.p(w_lp), rt.p(g), out_f, rt.p(dx), in_f, hdt,
+                                         L.MUL_NONE, None, 0, None, rt.p(ws), ws.numel(), rt.stream()), "hs_linear_bwd")
+            defer.hold(x, g)
         return dx, dw, db, None, None, dres, None
 
 
@@ -449,10 +452,13 @@ class MlpGeluFn(Function):
         if grouped:
             L.check(_lib().hs_wgrad_group_begin(st), "hs_wgrad_group_begin")
         try:
-            L.check(_lib().hs_linear_bwd(hdt, rt.p(h), M, hid, C.byref(lin2), rt.p(w2_lp), rt.p(dy), out_f, rt.p(dpre), hid, hdt,
-                                         L.MUL_GELU_GRAD, rt.p(pre), hid, None, rt.p(ws), n2, st), "hs_linear_bwd")
-            L.check(_lib().hs_linear_bwd(hdt, rt.p(x), M, in_f, C.byref(lin1), rt.p(w1_lp), rt.p(dpre), hid, rt.p(dx), in_f, hdt,
-                                         L.MUL_NONE, None, 0, None, rt.p(ws, n2), n1, st), "hs_linear_bwd")
+            # (the separate launches of the non-grouped branch may wait in the stream's deferred set, see LinearFn)
+            with rt.wgrad_defer_scope((w1, b1, w2, b2), allow=not grouped) as defer:
+                L.check(_lib().hs_linear_bwd(hdt, rt.p(h), M, hid, C.byref(lin2), rt.p(w2_lp), rt.p(dy), out_f, rt.p(dpre), hid,
+                                             hdt, L.MUL_GELU_GRAD, rt.p(pre), hid, None, rt.p(ws), n2, st), "hs_linear_bwd")
+                L.check(_lib().hs_linear_bwd(hdt, rt.p(x), M, in_f, C.byref(lin1), rt.p(w1_lp), rt.p(dpre), hid, rt.p(dx), in_f,
+                                             hdt, L.MUL_NONE, None, 0, None, rt.p(ws, n2), n1, st), "hs_linear_bwd")
+                defer.hold(h, dy, x, dpre)
         finally:
             if grouped:
                 L.check(_lib().hs_wgrad_group_end(st), "hs_wgrad_group_end")
@@ -659,6 +665,13 @@ class MHAFn(Function):
 
     @staticmethod
     def backward(ctx, dy):
+        # every projection's weight / bias gradient may wait in the stream's deferred set (see LinearFn): the node's serial chain
+        # is then its data-gradient GEMMs and the attention core
+        with rt.wgrad_defer_scope(ctx.saved_tensors[7:14]) as defer:
+            return MHAFn._backward(ctx, dy, defer)
+
+    @staticmethod
+    def _backward(ctx, dy, defer):
         (query, key, mask, q_t, k_t, saved, ctxv, in_w, in_b, q_w, k_w, v_w, out_w, out_b,
          lp_in, lp_q, lp_k, lp_v, lp_out) = ctx.saved_tensors
         meta, seed, packed, (q_off, k_off, v_off), (q_ld, k_ld, v_ld), has_res = ctx.meta
@@ -712,6 +725,7 @@ class MHAFn(Function):
         sv_b, ws_b = rt.query(lib.hs_attention_query, d)
         dq_t = torch.empty_like(q_t)
         dk_t = dq_t if k_t is q_t else torch.empty_like(k_t)
+        defer.hold(ctxv, dy, query, key, dq_t, dk_t)      # the x and dy of the projections' deferred gradients
         ws = rt.workspace(ws_b, dev)
         L.check(lib.hs_attention_bwd(C.byref(d), rt.p(q_t, q_off * es), rt.p(k_t, k_off * es), rt.p(v_t, v_off * es),
                                      rt.p(dctx), rt.p(dq_t, q_off * es), rt.p(dk_t, k_off * es), rt.p(dk_t, v_off * es),

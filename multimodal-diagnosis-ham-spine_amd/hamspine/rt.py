@@ -154,6 +154,169 @@ def grad_buffer_like(param):
     return torch.empty_like(param)
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# Deferred head-path weight gradients (hs_wgrad_defer_*).  The Linear nodes between the towers (fusion block, head, image
+# projection) launch only their data-gradient GEMMs where autograd runs them; their weight and bias gradients wait in a
+# per-stream set and run as one grouped GEMM grid plus one column-sum pair -- at the entry of the next whole-tower backward,
+# or from an end-of-backward callback.  A node defers only when nothing can read its gradients before that point.
+# ------------------------------------------------------------------------------------------------------------------
+_wd_sets = {}           # raw stream handle -> _DeferSet
+
+
+class _DeferSet:
+    def __init__(self, stream, alive):
+        self.stream = stream        # torch.cuda.Stream the set's launches go to
+        self.alive = alive          # weak reference to the token the pass's end-of-backward callback holds
+        self.keep = []              # operands of the deferred problems: alive until the flush has been enqueued
+
+
+class _PassToken:
+    pass
+
+
+def _wd_drop_stale():
+    """A backward pass that ends in an exception runs no engine callback -- the engine discards it, and with it the token it
+    holds.  The sets of such a pass are still here, their operands may be gone: they are dropped without a launch, by the next
+    backward pass or by whoever looks first."""
+    for key in [k for k, s in _wd_sets.items() if s.alive() is None]:
+        s = _wd_sets.pop(key)
+        L.lib().hs_wgrad_defer_abort(C.c_void_p(key))
+        s.keep.clear()
+
+
+def wgrad_defer_enabled():
+    import os
+    return os.environ.get("HAMSPINE_WGRAD_DEFER", "1") != "0"
+
+
+def _wgrad_defer_allowed(params):
+    if _grad_arena:      # data-parallel buckets mark "gradient final" when autograd hands it over
+        return False
+    import torch.distributed as dist
+    # a process group exists: some data-parallel wrapper may be reading gradients at hand-over (torch's DistributedDataParallel
+    # registers its gradient-ready hooks on the accumulator nodes in C++, where Python cannot see them)
+    if dist.is_available() and dist.is_initialized():
+        return False
+    for p_ in params:
+        if p_ is None:
+            continue
+        # not a leaf (a cast, a slice, a product of parameters): further autograd nodes read the gradient right away.  An existing
+        # .grad: AccumulateGrad would add the still unfilled buffer.  Hooks (tensor hooks, optimizer-in-backward, hamspine.ddp)
+        # read the gradient when autograd hands it over.
+        if not p_.is_leaf or p_.grad is not None or p_._backward_hooks or getattr(p_, "_post_accumulate_grad_hooks", None):
+            return False
+    return True
+
+
+_wd_seen = {}           # autograd graph task id -> ids of the parameters whose gradient a scoped node of that pass has produced
+
+
+def _wd_second_use(task, params):
+    """True when one of params already got a gradient from an earlier node of this backward pass.  Autograd then SUMS the two
+    gradients as soon as the second node returns -- an earlier deferred one has to be launched before that, and this one cannot
+    wait either."""
+    seen = _wd_seen.get(task)
+    if seen is None:
+        while len(_wd_seen) >= 8:               # passes nest at most a few deep (re-entrant backward); older ones are over
+            _wd_seen.pop(min(_wd_seen))
+        seen = _wd_seen[task] = set()
+    ids = [id(p_) for p_ in params if p_ is not None]
+    dup = any(i in seen for i in ids)
+    seen.update(ids)
+    return dup
+
+
+class wgrad_defer_scope:
+    """with wgrad_defer_scope(params) as d: the hs_linear_bwd calls inside launch their data gradients only (d.on) and the caller
+    hands d.hold(...) every x and dy of those calls.  allow False, or not allowed for these parameters: the calls run as ever
+    (outside a scope an open set is suspended, so no other caller of hs_linear_bwd feeds it)."""
+
+    def __init__(self, params, allow=True):
+        self.params = params
+        self.allow = allow
+        self.on = False
+        self._set = None
+
+    def __enter__(self):
+        if not wgrad_defer_enabled():
+            return self
+        _wd_drop_stale()
+        task = torch._C._current_graph_task_id()
+        if task < 0:                               # not inside a backward pass: nobody would flush
+            return self
+        cur = torch.cuda.current_stream()
+        if _wd_second_use(task, self.params):      # a parameter used twice in this pass: everything pending goes out now
+            others = [o.stream for k, o in _wd_sets.items() if k != cur.cuda_stream]
+            wgrad_defer_flush_all()
+            for o in others:
+                cur.wait_stream(o)
+            return self
+        if not self.allow or not _wgrad_defer_allowed(self.params):
+            return self                            # an open set stays suspended: the calls inside run as ever
+        key = cur.cuda_stream
+        s = _wd_sets.get(key)
+        if s is None:
+            live = [o.alive() for o in _wd_sets.values()]
+            token = live[0] if live else None
+            if token is None:                      # first set of this pass: its end-of-backward flush
+                from torch.autograd import Variable
+                token = _PassToken()
+                Variable._execution_engine.queue_callback(lambda token=token: wgrad_defer_flush_all())
+            s = _wd_sets[key] = _DeferSet(cur, _weakref.ref(token))
+        L.check(L.lib().hs_wgrad_defer_begin(C.c_void_p(key)), "hs_wgrad_defer_begin")
+        self._set, self.on = s, True
+        return self
+
+    def hold(self, *tensors):
+        if self.on:
+            self._set.keep.extend(t for t in tensors if t is not None)
+
+    def __exit__(self, et, ev, tb):
+        if self.on:
+            L.check(L.lib().hs_wgrad_defer_suspend(C.c_void_p(self._set.stream.cuda_stream)), "hs_wgrad_defer_suspend")
+        return False
+
+
+def _wgrad_defer_flush_one(key):
+    s = _wd_sets.pop(key, None)
+    if s is None:
+        return
+    lib = L.lib()
+    st = C.c_void_p(key)
+    try:
+        if lib.hs_wgrad_defer_pending(st) > 0:
+            with torch.cuda.stream(s.stream):
+                nbytes = int(lib.hs_wgrad_defer_ws_bytes(st))
+                if nbytes < 0:
+                    L.check(L.HS_ERR_ARG, "hs_wgrad_defer_ws_bytes")
+                ws = workspace(nbytes, s.stream.device)
+                L.check(lib.hs_wgrad_defer_flush(st, p(ws), ws.numel()), "hs_wgrad_defer_flush")
+    finally:
+        lib.hs_wgrad_defer_abort(st)        # no-op after a flush; drops the set when something above raised
+        s.keep.clear()
+
+
+def wgrad_defer_flush_all():
+    """launch every open set of this backward pass (the whole-tower backward executors call this at their entry; it is also the
+    end-of-backward callback a pass queues when it opens its first set)"""
+    _wd_drop_stale()
+    for key in list(_wd_sets):
+        _wgrad_defer_flush_one(key)
+
+
+def wgrad_defer_counters():
+    """process totals: problems deferred, problems flushed, grouped GEMM launches, column-sum launches, table uploads"""
+    out = (C.c_int64 * 5)()
+    L.lib().hs_wgrad_defer_counters(out)
+    return dict(zip(("deferred", "flushed", "grouped_launches", "colsum_launches", "table_uploads"), [int(v) for v in out]))
+
+
+def wgrad_defer_open():
+    """True while a set of a running backward pass is open (tests check that a finished or failed backward leaves none)"""
+    _wd_drop_stale()
+    return bool(_wd_sets)
+
+
 def hs_dtype(t_or_dtype):
     dt = t_or_dtype.dtype if isinstance(t_or_dtype, torch.Tensor) else t_or_dtype
     if dt == torch.bfloat16:

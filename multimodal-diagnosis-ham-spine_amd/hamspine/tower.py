@@ -283,6 +283,7 @@ class ResNetTowerFn(Function):
             raise RuntimeError("hamspine.tower: backward through a tower a second time: its saved activations are freed by the "
                                "first backward (retain_graph=True is not supported on the tower nodes)")
         _ = ctx.saved_tensors                        # raises if an output was modified in place since the forward
+        rt.wgrad_defer_flush_all()                   # the head path's deferred weight gradients: one grouped grid in front of the tower
         n = len(ent.taps)
         ptrs = (C.c_void_p * n)()
         keep = []
@@ -479,6 +480,7 @@ class BertTowerFn(Function):
             raise RuntimeError("hamspine.tower: backward through a tower a second time: its saved activations are freed by the "
                                "first backward (retain_graph=True is not supported on the tower nodes)")
         _ = ctx.saved_tensors
+        rt.wgrad_defer_flush_all()                   # (as the image tower's backward)
         dy = dy.contiguous()
         if dy.dtype != ent.dtype:
             dy = dy.to(ent.dtype)
