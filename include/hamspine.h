@@ -710,7 +710,8 @@ hs_status hs_dwconv_bwd(int32_t dtype, const void* x, const float* w, const void
    stochastic depth keep/(1-p)) may be NULL. */
 hs_status hs_layerscale_fwd(int32_t dtype, const void* u, const float* gamma, const float* rowscale, int32_t rows_per_sample,
                             const void* res, void* out, int64_t M, int32_t C, void* stream);
-/* du (optional) = gamma * rowscale * dy ; dgamma[c] = sum_m rowscale * dy * u. */
+/* du (optional) = gamma * rowscale * dy ; dgamma[c] = sum_m rowscale * dy * u.  C % 4 == 0 as in the forward (refused
+   otherwise); ws holds at least hs_layerscale_ws_bytes(M, C) bytes. */
 hs_status hs_layerscale_bwd(int32_t dtype, const void* dy, const void* u, const float* gamma, const float* rowscale,
                             int32_t rows_per_sample, void* du, float* dgamma, void* ws, int64_t ws_bytes, int64_t M, int32_t C,
                             void* stream);
@@ -737,7 +738,9 @@ hs_status hs_kan_features_fwd(const float* x, const float* grid, float* feat, in
                               int32_t order, int32_t base_act, void* stream);
 hs_status hs_kan_features_bwd(const float* x, const float* grid, const float* dfeat, float* dx, int64_t B, int32_t in_f,
                               int32_t grid_size, int32_t order, int32_t base_act, void* stream);
-/* wcat[o] = [base_w[o,:] | spline_w[o,i,:]*scaler[o,i] ...]  (scaler may be NULL), nb = grid_size + order. */
+/* wcat[o] = [base_w[o,:] | spline_w[o,i,:]*scaler[o,i] ...]  (scaler may be NULL), nb = grid_size + order.
+   hs_kan_unpack_wgrad: d_base = the base columns of dwcat, d_spline = dwcat * scaler, d_scaler = <dwcat, spline_w> over nb
+   (each d_* optional).  Both refuse out_f, in_f or nb < 1. */
 hs_status hs_kan_pack_weight(const float* base_w, const float* spline_w, const float* scaler, float* wcat, int32_t out_f,
                              int32_t in_f, int32_t nb, void* stream);
 hs_status hs_kan_unpack_wgrad(const float* dwcat, const float* spline_w, const float* scaler, float* d_base, float* d_spline,
@@ -746,7 +749,9 @@ hs_status hs_kan_unpack_wgrad(const float* dwcat, const float* spline_w, const f
    coef*(cv^2(importance)+cv^2(load)), plus everything the backward needs (p, top: (B,17) int32, z, sigma,
    loadrow, d_imp[E], d_load[E]).  E <= 16.
    noise: optional (B,E) standard-normal draw to use instead of the counter RNG (NULL = draw from `seed`): the reference's
-   torch.randn_like(clean_logits), moe.py:247, recorded by a caller that wants its gating reproduced exactly. */
+   torch.randn_like(clean_logits), moe.py:247, recorded by a caller that wants its gating reproduced exactly.
+   hs_moe_gate_bwd: d_clean (and d_raw, optional) from dgates and g_loss (optional: NULL = no loss gradient).  Like the forward
+   it refuses anything but 1 <= k <= E <= 16, and B < 1; noisy gating with d_raw wanted needs raw_noise. */
 hs_status hs_moe_gate_fwd(const float* clean, const float* raw_noise, const float* noise, int32_t B, int32_t E, int32_t k, int32_t noisy,
                           float noise_eps, uint64_t seed, float coef, float* gates, float* p, int32_t* top, float* z,
                           float* sigma, float* loadrow, float* loss, float* d_imp, float* d_load, void* stream);
@@ -754,7 +759,8 @@ hs_status hs_moe_gate_bwd(const float* clean, const float* raw_noise, const floa
                           const float* sigma, const float* dgates, const float* g_loss, const float* d_imp,
                           const float* d_load, int32_t B, int32_t E, int32_t k, int32_t noisy, float* d_clean, float* d_raw,
                           void* stream);
-/* y[b,:] = sum_e gates[b,e]*outs[e][b,:] (dense form of SparseDispatcher.combine, moe.py:86-103) and its backward. */
+/* y[b,:] = sum_e gates[b,e]*outs[e][b,:] (dense form of SparseDispatcher.combine, moe.py:86-103) and its backward.
+   1 <= E <= 16; B < 1 or O < 1 is refused. */
 hs_status hs_moe_combine_fwd(const float* gates, const float* const* outs, float* y, int32_t B, int32_t E, int32_t O,
                              void* stream);
 hs_status hs_moe_combine_bwd(const float* gates, const float* const* outs, const float* dy, float* const* douts,

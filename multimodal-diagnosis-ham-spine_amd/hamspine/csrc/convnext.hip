@@ -530,7 +530,8 @@ hs_status hs_layerscale_fwd(int32_t dtype, const void* u, const float* gamma, co
 hs_status hs_layerscale_bwd(int32_t dtype, const void* dy, const void* u, const float* gamma, const float* rowscale,
                             int32_t rows_per_sample, void* du, float* dgamma, void* ws, int64_t ws_bytes, int64_t M, int32_t C,
                             void* stream) {
-    HS_REQUIRE(dy && u && gamma && dgamma && ws && M > 0 && C > 0, "layerscale_bwd: null argument");
+    HS_REQUIRE(dy && u && gamma && dgamma && ws && M > 0, "layerscale_bwd: null argument");
+    HS_REQUIRE(C > 0 && C % 4 == 0, "layerscale_bwd: C=%d must be a multiple of 4", C);
     HS_REQUIRE(ws_bytes >= hs_layerscale_ws_bytes(M, C), "layerscale_bwd: workspace too small");
     HS_REQUIRE(!rowscale || rows_per_sample > 0, "layerscale_bwd: rows_per_sample");
     return CN_DISPATCH_T(dtype, layerscale_bwd_t, dy, u, gamma, rowscale, rows_per_sample, du, dgamma, (float*)ws, M, C,

@@ -542,6 +542,7 @@ hs_status hs_kan_features_bwd(const float* x, const float* grid, const float* df
 hs_status hs_kan_pack_weight(const float* base_w, const float* spline_w, const float* scaler, float* wcat, int32_t out_f,
                              int32_t in_f, int32_t nb, void* stream) {
     HS_REQUIRE(base_w && spline_w && wcat, "kan_pack_weight: null argument");
+    HS_REQUIRE(out_f >= 1 && in_f >= 1 && nb >= 1, "kan_pack_weight: out=%d in=%d nb=%d must be positive", out_f, in_f, nb);
     hipLaunchKernelGGL(kan_pack_weight_kernel, dim3(grid_for((long long)out_f * in_f * (1 + nb))), dim3(256), 0,
                        (hipStream_t)stream, base_w, spline_w, scaler, wcat, out_f, in_f, nb);
     HS_LAUNCH_CHECK();
@@ -550,6 +551,7 @@ hs_status hs_kan_pack_weight(const float* base_w, const float* spline_w, const f
 hs_status hs_kan_unpack_wgrad(const float* dwcat, const float* spline_w, const float* scaler, float* d_base, float* d_spline,
                               float* d_scaler, int32_t out_f, int32_t in_f, int32_t nb, void* stream) {
     HS_REQUIRE(dwcat && spline_w, "kan_unpack_wgrad: null argument");
+    HS_REQUIRE(out_f >= 1 && in_f >= 1 && nb >= 1, "kan_unpack_wgrad: out=%d in=%d nb=%d must be positive", out_f, in_f, nb);
     hipLaunchKernelGGL(kan_unpack_wgrad_kernel, dim3(grid_for((long long)out_f * in_f)), dim3(256), 0, (hipStream_t)stream,
                        dwcat, spline_w, scaler, d_base, d_spline, d_scaler, out_f, in_f, nb);
     HS_LAUNCH_CHECK();
@@ -574,6 +576,8 @@ hs_status hs_moe_gate_bwd(const float* clean, const float* raw_noise, const floa
                           const float* d_load, int32_t B, int32_t E, int32_t k, int32_t noisy, float* d_clean, float* d_raw,
                           void* stream) {
     HS_REQUIRE(clean && p && top && z && sigma && dgates && d_imp && d_load && d_clean, "moe_gate_bwd: null argument");
+    HS_REQUIRE(B >= 1 && E >= 1 && E <= MOE_MAXE && k >= 1 && k <= E, "moe_gate_bwd: need B >= 1 and 1 <= k <= E <= %d", MOE_MAXE);
+    HS_REQUIRE(!noisy || !d_raw || raw_noise, "moe_gate_bwd: d_raw of noisy gating needs raw_noise");
     hipLaunchKernelGGL(moe_gate_bwd_kernel, dim3(ceil_div(B, 64)), dim3(64), 0, (hipStream_t)stream, clean, raw_noise, p,
                        (const int*)top, z, sigma, dgates, g_loss, d_imp, d_load, B, E, k, noisy, d_clean, d_raw);
     HS_LAUNCH_CHECK();
@@ -582,6 +586,7 @@ hs_status hs_moe_gate_bwd(const float* clean, const float* raw_noise, const floa
 hs_status hs_moe_combine_fwd(const float* gates, const float* const* outs, float* y, int32_t B, int32_t E, int32_t O,
                              void* stream) {
     HS_REQUIRE(gates && outs && y && E >= 1 && E <= MOE_MAXE, "moe_combine: bad argument");
+    HS_REQUIRE(B >= 1 && O >= 1, "moe_combine: B=%d and O=%d must be positive", B, O);
     ExpertPtrs ep;
     memset(&ep, 0, sizeof(ep));
     for (int e = 0; e < E; ++e) ep.p[e] = outs[e];
@@ -593,6 +598,7 @@ hs_status hs_moe_combine_fwd(const float* gates, const float* const* outs, float
 hs_status hs_moe_combine_bwd(const float* gates, const float* const* outs, const float* dy, float* const* douts,
                              float* dgates, int32_t B, int32_t E, int32_t O, void* stream) {
     HS_REQUIRE(gates && outs && dy && douts && dgates && E >= 1 && E <= MOE_MAXE, "moe_combine_bwd: bad argument");
+    HS_REQUIRE(B >= 1 && O >= 1, "moe_combine_bwd: B=%d and O=%d must be positive", B, O);
     ExpertPtrs ep;
     ExpertPtrsMut dp;
     memset(&ep, 0, sizeof(ep));
