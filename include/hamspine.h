@@ -819,8 +819,8 @@ hs_status hs_attention_bwd(const hs_attn_desc* d, const void* q, const void* k, 
                            void* dk, void* dv, void* saved, int64_t saved_bytes, void* ws, int64_t ws_bytes,
                            void* stream);
 
-/* weight-gradient side stream inside the composites below: 1 on (default; env HAMSPINE_OVERLAP=0 turns it off),
-   0 off = every kernel of a composite runs on the caller's stream (used to time kernels in isolation). */
+/* weight-gradient side stream inside the composites below: 1 on (or env HAMSPINE_OVERLAP=1), 0 off (default) = every
+   kernel of a composite runs on the caller's stream. */
 void hs_set_overlap(int32_t on);
 /* Gradient milestones for bucketed data-parallel exchange (reference mibf_net/train_resnet.py:134: DDP starts a bucket's
    all-reduce when its last gradient is ready).  The NEXT hs_resnet_bwd / hs_bert_bwd on the calling thread records

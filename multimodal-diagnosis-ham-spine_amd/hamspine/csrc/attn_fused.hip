@@ -13,6 +13,8 @@
 // {4g..4g+3} and {16+4g..16+4g+3}; MFMA's k index is only a summation index, so V is fetched in the same permuted key
 // order (two ds_read_b64_tr_b16 at rows 4g and 16+4g) and no transpose through LDS is needed.
 #include "gemm_core.h"
+#include "hs_internal.h"
+#include "hs_switch.h"
 
 namespace hs {
 
@@ -1040,10 +1042,6 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_long_kernel(const AttnFuse
 // host side: eligibility + launch.  Returns 1 when the fused kernel ran, 0 when the shape is not covered, < 0 on error.
 // cu: packed rows (see packed_span), or NULL.  The caller (bert_check in blocks.hip, hamspine.tower.bert_pack_supported) has checked that the shape is one the
 // packed kernels cover; a launch that cannot honour cu is an error, never the padded computation.
-bool fused_attention_enabled() {             // HAMSPINE_FUSED_ATTENTION=0: the unfused attention path (read once)
-    static const bool on = [] { const char* e = getenv("HAMSPINE_FUSED_ATTENTION"); return !(e && e[0] == '0'); }();
-    return on;
-}
 static bool packed_shape_ok(const hs_attn_desc& d) {
     return d.dtype == HS_BF16 && d.hd == 64 && d.Lq == d.Lk && d.Lk <= 128 && d.q_bs == (long long)d.Lq * d.q_ld &&
            d.k_bs == (long long)d.Lk * d.k_ld && d.v_bs == (long long)d.Lk * d.v_ld && d.o_bs == (long long)d.Lq * d.o_ld;
@@ -1051,7 +1049,7 @@ static bool packed_shape_ok(const hs_attn_desc& d) {
 int attention_fwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, void* o, void* P, void* Pd,
                         int ldP, hipStream_t s, const int* cu) {
     if (cu && !packed_shape_ok(d)) return -1;
-    const bool enabled = fused_attention_enabled();
+    const bool enabled = sw::fused_attention();
     // head dim 64 (BERT) or 32 (the fusion modules' 8-head attention over 256 features), any number of queries (128-row
     // chunks on grid.y), at most 128 keys -- 512 at head dim 64 (257..512 keys: 64-row chunks)
     const bool wide = d.hd == 64 && d.Lk > 256;
@@ -1105,7 +1103,7 @@ int attention_bwd_fused(const hs_attn_desc& d, const void* q, const void* k, con
                         void* dv, const void* P, int ldP, void* scratch, long long scratch_bytes, const void* O, hipStream_t s,
                         const int* cu) {
     if (cu && !packed_shape_ok(d)) return -1;
-    const bool enabled = fused_attention_enabled();
+    const bool enabled = sw::fused_attention();
     if (!enabled || d.dtype != HS_BF16 || (d.hd != 64 && d.hd != 32) || d.Lq < 1 || d.Lk < 1 || d.Lk > (d.hd == 64 ? 512 : 128) || ldP % 4 != 0 || ldP < d.Lk) return cu ? -1 : 0;
     const bool long_keys = d.Lk > 128;
     const long long rows = (long long)d.B * d.H * d.Lq;

@@ -8,8 +8,8 @@
 #include <mutex>
 #include <unordered_map>
 #include <vector>
-#include <stdlib.h>
-#include "hs_common.h"
+#include "hs_internal.h"
+#include "hs_switch.h"
 #include "pw_stream.h"
 
 namespace hs {
@@ -22,66 +22,6 @@ __global__ __launch_bounds__(256) void gather3_kernel(const float* __restrict__ 
     const int w = i / n, k = i - w * n;
     dst[i] = w == 0 ? a[k] : (w == 1 ? b[k] : c[k]);
 }
-
-int gemm_impl(const hs_gemm_params* p, hipStream_t stream, const ResGather* rg = nullptr);
-int gemm_stat_rows(const hs_gemm_params* p);
-int gemm_bn_finish_rows(const hs_gemm_params* p);
-int gemm_tile_rows(const hs_gemm_params* p);
-int gemm_bnb_finish_rows(const hs_gemm_params* p);
-// lean forms of the image tower's BatchNorm / max-pool passes (norm.hip; bf16 only, see img_lean below)
-int bn_fwd_dsres(const hs_bn_params* p, const void* c_ds, const float* scale_ds, const float* shift_ds, hipStream_t s);
-int bn_relu_maxpool_fwd(const void* c, const float* scale, const float* shift, void* y, void* idx, int N, int H, int W, int C,
-                        hipStream_t s);
-int bn_bwd_pooled(const hs_bn_bwd_params* p, const void* idx, int N, int H, int W, hipStream_t s);
-long long bn_bwd_pair_ws_bytes(long long M, int C);
-int bn_bwd_pair(const hs_bn_bwd_params* p, const hs_bn_bwd_params* pd, hipStream_t s);
-void gemm_group_set_immediate_hook(int (*fn)(void*), void* ctx);
-struct GemmGroup;
-GemmGroup* gemm_group_open(hipStream_t s, long long slot);   // slot: any key that is stable across steps (its device table is cached)
-// k_cols (device, or NULL): the operands' K columns are chunk-compacted and the walk ends behind column *k_cols (GemmArgs.k_cols).
-// Only a QUEUED problem can carry it -- one that would be launched on its own is refused -- and gemm_group_takes_k_cols() says
-// beforehand whether K-contiguous bf16 problems are queued at all (they are unless a measurement override is armed).
-int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s, const int* k_cols = nullptr);
-bool gemm_group_takes_k_cols();
-int gemm_group_flush(GemmGroup* g, hipStream_t s);
-void gemm_group_upload_on_stream(GemmGroup* g);       // a changed problem table travels on the stream, no synchronise
-long long gemm_group_uploads(const GemmGroup* g);
-long long gemm_group_launches(const GemmGroup* g);
-int colsum_multi(int count, const int* dtype, const void* const* x, const long long* M, const int* N, const int* ld, float* const* out,
-                 float* const* ws, hipStream_t s, int* launches);
-bool fused_attention_enabled();
-int attention_bwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, const void* dO, void* dq, void* dk,
-                        void* dv, const void* P, int ldP, void* scratch, long long scratch_bytes, const void* O, hipStream_t s,
-                        const int* cu);
-int attention_fwd_fused(const hs_attn_desc& d, const void* q, const void* k, const void* v, void* o, void* P, void* Pd, int ldP,
-                        hipStream_t s, const int* cu);
-// packed-row forms of the row-wise kernels (norm.hip, elem.hip): nrows / row_of / inv / packed_of NULL = every row, as the C ABI
-// entries.  Kernels that SUM over rows (LayerNorm backward, column sums, the transposes a weight gradient reads) take inv and walk
-// the padded rows, so that their sums have the padded tower's terms in the padded tower's order: the results are bitwise its results
-int ln_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, long long M, int H,
-           float eps, hipStream_t s, const int* nrows);
-int ln_bwd(int dtype, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
-           float* dbeta, float* ws, long long ws_bytes, long long M, int H, hipStream_t s, const int* inv);
-int ln_bwd_pre(int dtype, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx,
-               float* dgamma, float* dbeta, void* dx_dropped, float* dbias, float p, unsigned long long seed, float* ws,
-               long long ws_bytes, long long M, int H, hipStream_t s, const int* inv);
-int transpose_bf16_multi_rows(int count, const void* const* src, void* const* dst, const int32_t* R, const int32_t* Cc,
-                              const int64_t* ld_src, const int64_t* ld_dst, const int* inv, const unsigned char* tok, const int* kc,
-                              const int* kc_pos, hipStream_t stream);
-int colsum_rows(int dtype, const void* x, long long M, int N, int ld, float* out, void* ws, long long ws_bytes, int accumulate,
-                const int* inv, hipStream_t s);
-int dropout_rows(int dtype, const void* x, void* out, long long M, int H, float p, unsigned long long seed, const int* nrows,
-                 const int* row_of, hipStream_t s);
-long long bert_row_map_bytes(int B, int L);
-int bert_row_map(const int64_t* mask, int B, int L, int* map, hipStream_t s);
-int bert_unpack_rows(const void* y, void* out, long long rows, long long row_bytes, const int* packed_of, hipStream_t s);
-int bert_pack_rows(const void* dy, void* dst, long long rows, long long row_bytes, const int* nrows, const int* row_of,
-                   const int* word_src, int* word_dst, hipStream_t s);
-int bert_embed_fwd_rows(int dtype, const int64_t* ids, const float* word, const float* pos, const float* type0, const float* gamma,
-                        const float* beta, void* sum_out, void* y, float* mean, float* rstd, long long tokens, int L, int H, int V,
-                        float eps, float dropout_p, unsigned long long seed, const int* nrows, const int* row_of, hipStream_t stream);
-int bert_embed_bwd_rows(int dtype, const int64_t* ids, const void* dsum, float* dword, float* dpos, int B, int L, int H, int V,
-                        int pad_id, const int* nrows, const int* row_of, const int* packed_of, hipStream_t s);
 
 static inline long long align_up(long long v, long long a) { return (v + a - 1) / a * a; }
 static inline int esize(int dt) { return dt == HS_BF16 ? 2 : 4; }
@@ -108,6 +48,12 @@ struct Run {
     int dt;
     bool plan;
     Arena saved, ws;
+    explicit Run(int dtype) : s(nullptr), dt(dtype), plan(true) { saved.plan = ws.plan = true; }   // plan mode: sizes only
+    Run(int dtype, void* saved_base, long long saved_bytes, void* ws_base, long long ws_bytes, hipStream_t stream)
+        : s(stream), dt(dtype), plan(false) {
+        saved.base = (char*)saved_base; saved.cap = saved_bytes;
+        ws.base = (char*)ws_base; ws.cap = ws_bytes;
+    }
     // second stream for work that is off the critical path of a backward (weight / bias gradients): it is
     // forked behind the producers of its inputs and joined before the composite returns
     hipStream_t side = nullptr;
@@ -152,16 +98,8 @@ static std::mutex g_side_mu;
 // epilogue work: with workgroups that live 7.8 instead of 12.4 us a single GEMM fills the chip well enough that running two
 // at once only makes them contend (C2 step 14.5 ms with the side stream, 12.6 ms without; it was 21.5 -> 19.7 ms the other
 // way round when it was introduced).  HAMSPINE_OVERLAP=1 / hs_set_overlap(1) switch it on.
-static int g_overlap = -1;   // -1: take HAMSPINE_OVERLAP from the environment on first use
-static bool overlap_enabled() {
-    if (g_overlap < 0) {
-        const char* e = getenv("HAMSPINE_OVERLAP");
-        g_overlap = (e && e[0] == '1') ? 1 : 0;
-    }
-    return g_overlap == 1;
-}
 static int side_setup(Run& r) {
-    if (r.plan || !overlap_enabled()) return HS_OK;
+    if (r.plan || !sw::overlap()) return HS_OK;
     int dev = 0;
     HS_CHECK_HIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= 16) return HS_OK;
@@ -205,18 +143,6 @@ static int side_join(Run& r) {
     r.side_used = false;
     return HS_OK;
 }
-static void run_init(Run& r, int dt, bool plan, void* saved, long long saved_bytes, void* ws, long long ws_bytes,
-                     hipStream_t s) {
-    r.s = s;
-    r.dt = dt;
-    r.plan = plan;
-    r.saved.base = (char*)saved;
-    r.saved.cap = saved_bytes;
-    r.saved.plan = plan;
-    r.ws.base = (char*)ws;
-    r.ws.cap = ws_bytes;
-    r.ws.plan = plan;
-}
 #define RUN_CHECK_ARENAS(r, what)                                                                          \
     do {                                                                                                   \
         if (!(r).plan && ((r).saved.overflow || (r).ws.overflow)) {                                        \
@@ -234,18 +160,11 @@ static void run_init(Run& r, int dt, bool plan, void* saved, long long saved_byt
 // weight gradients, 2 BERT weight-gradient GEMMs, 4 transposes, 8 BatchNorm forward, 16 BatchNorm backward, 64 weight casts,
 // 128 LayerNorm backward, 256 attention cores, 512 ResNet data-gradient convolutions, 1024 BERT data-gradient GEMMs.
 // The switch exists only in measurement builds (make EXTRA=-DHS_MEASURE, what tools/knockout.sh builds): a release library
-// ignores the variable, hs_measure_build() reports which one is loaded and bench.py refuses to run on a measurement build.
-#ifdef HS_MEASURE
-static int knock() {
-    static const int v = [] { const char* e = getenv("HAMSPINE_KNOCKOUT"); return e ? atoi(e) : 0; }();
-    return v;
-}
-#else
-static constexpr int knock() { return 0; }
-#endif
+// ignores the variable (sw::knockout() is constexpr 0), hs_measure_build() reports which one is loaded and bench.py refuses to
+// run on a measurement build.
 #define CALLK(r, bit, expr)                                        \
     do {                                                           \
-        if (!(r).plan && !(knock() & (bit))) HS_PROPAGATE(expr);   \
+        if (!(r).plan && !(sw::knockout() & (bit))) HS_PROPAGATE(expr);   \
     } while (0)
 
 // ---- gradient milestones (hs_grad_milestones) ---------------------------------------------------------------------
@@ -308,13 +227,13 @@ static int gemm_splitk(Run& r, hs_gemm_params& p, bool may_defer = false, const 
             set_error("gemm_splitk: workspace too small");
             return HS_ERR_ARG;
         }
-        if (may_defer && (knock() & 1)) {
+        if (may_defer && (sw::knockout() & 1)) {
         } else if (defer) HS_PROPAGATE(gemm_group_add(p.b_kind == HS_B_CONV ? r.grp_conv : r.grp_pw, &p, r.s));
         else HS_PROPAGATE(gemm_impl(&p, r.s, rg));
     }
     if (defer) return HS_OK;                 // the slabs stay allocated until the grouped launch has run
     // with a side stream, slabs of consecutive GEMMs may be live concurrently: keep them until the composite ends
-    if (r.plan ? !overlap_enabled() : !r.side) r.ws.release(mk);
+    if (r.plan ? !sw::overlap() : !r.side) r.ws.release(mk);
     return HS_OK;
 }
 
@@ -350,7 +269,7 @@ static int attention_fwd_run(Run& r, const hs_attn_desc& d, const void* q, const
     HS_PROPAGATE(attn_check(d));
     AttnLayout l = attn_layout(d, r, false);
     const int BH = d.B * d.H;
-    if (!r.plan && (knock() & 256)) return HS_OK;
+    if (!r.plan && (sw::knockout() & 256)) return HS_OK;
     if (!r.plan && !r.saved.overflow && !r.ws.overflow) {
         // BERT shape (bf16, head dim 64, <= 128 tokens): one fused kernel, scores stay in registers (csrc/attn_fused.hip)
         const int fused = attention_fwd_fused(d, q, k, v, o, l.P, l.Pd, l.ldP, r.s, r.pk_cu);
@@ -406,7 +325,7 @@ static int attention_bwd_run(Run& r, const hs_attn_desc& d, const void* q, const
     const int BH = d.B * d.H;
     const long long o_el = span_elems(d.B, d.o_bs, d.Lq, d.o_ld, d.H, d.hd);
     const long long p_el = (long long)BH * d.Lq * l.ldP;
-    if (!r.plan && (knock() & 256)) return HS_OK;
+    if (!r.plan && (sw::knockout() & 256)) return HS_OK;
     if (!r.plan && !r.saved.overflow && !r.ws.overflow) {
         // BERT shape: one fused kernel (csrc/attn_fused.hip) instead of four batched GEMMs and the softmax backward; beyond
         // 128 keys it keeps its f32 dQ slab in the dP buffer the unfused path would use
@@ -508,16 +427,9 @@ static int linear_fwd_run(Run& r, const void* x, long long M, int ldx, const hs_
     return HS_OK;
 }
 // parameter gradients: dw = dy^T x, db = colsum(dy)
-static bool fused_bias_grad_enabled() {     // HAMSPINE_FUSED_BIAS_GRAD=0: bias gradients by separate column-sum passes
-    static const bool on = [] {
-        const char* e = getenv("HAMSPINE_FUSED_BIAS_GRAD");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
 // a weight-gradient GEMM (bf16, unsplit) can produce the bias gradient as the row sums of its A operand
 static bool bias_in_wgrad(int dt, int out_f, int in_f, long long M) {
-    return dt == HS_BF16 && fused_bias_grad_enabled() && hs_gemm_suggest_split(out_f, in_f, (int)M, dt) <= 1;
+    return dt == HS_BF16 && sw::fused_bias_grad() && hs_gemm_suggest_split(out_f, in_f, (int)M, dt) <= 1;
 }
 // Caller-scoped grouping (hs_wgrad_group_begin / _end): between the two calls the K-contiguous weight-gradient GEMMs that
 // hs_linear_bwd issues on that stream are collected and run as one grouped grid at _end (an MLP's two Linear layers: two
@@ -560,7 +472,6 @@ static void wgrad_defer_push(hipStream_t s, int dtype, const void* x, long long 
     it->second.push_back(DeferredWgrad{dtype, x, dy, M, ldx, ldy, lin.in_f, lin.out_f, lin.dw, lin.db});
     g_wd_deferred.fetch_add(1, std::memory_order_relaxed);
 }
-static bool wgrad_nt_enabled();
 static int linear_wgrad_nt_run(Run& r, const void* xT, const void* dyT, long long M, int in_f, int out_f, float* dw, float* db,
                                int seg_rows, float* const* dw_seg, float* const* db_seg, const int* k_cols = nullptr);
 // bf16, compute-bound shapes (in*out/(in+out) FLOP per operand byte above the ridge; ConvNeXt's 512 <-> 2048 MLPs over
@@ -568,7 +479,7 @@ static int linear_wgrad_nt_run(Run& r, const void* xT, const void* dyT, long lon
 // K-contiguous GEMM, as the BertLayer backward does.  Long-K / small-output shapes stay on the split-K "tn" form (they are
 // HBM-bound and the transposes would double their traffic).
 static bool linear_wgrad_takes_nt(int dt, long long M, int ldx, const hs_linear& lin, int ldy) {
-    return lin.dw && dt == HS_BF16 && wgrad_nt_enabled() && M >= 2048 && M % 8 == 0 && lin.in_f % 8 == 0 && lin.out_f % 8 == 0 &&
+    return lin.dw && dt == HS_BF16 && sw::wgrad_nt() && M >= 2048 && M % 8 == 0 && lin.in_f % 8 == 0 && lin.out_f % 8 == 0 &&
            ldx % 8 == 0 && ldy % 8 == 0 && ldx >= lin.in_f && ldy >= lin.out_f &&
            (long long)lin.in_f * lin.out_f >= 256ll * (lin.in_f + lin.out_f);
 }
@@ -608,7 +519,7 @@ static int linear_wgrad_run(Run& r, const void* x, long long M, int ldx, const h
             r.group_nt = true;
             r.grp_nt = og;
         }
-        const bool fused_b = lin.db && (r.group_nt || hs_gemm_suggest_split(lin.out_f, lin.in_f, (int)M, r.dt) <= 1) && fused_bias_grad_enabled();
+        const bool fused_b = lin.db && (r.group_nt || hs_gemm_suggest_split(lin.out_f, lin.in_f, (int)M, r.dt) <= 1) && sw::fused_bias_grad();
         const int st_nt = linear_wgrad_nt_run(r, tB, tA, M, lin.in_f, lin.out_f, lin.dw, lin.db, 0, nullptr, nullptr);
         r.group_nt = keep_flag;
         r.grp_nt = keep_grp;
@@ -633,7 +544,7 @@ static int linear_wgrad_run(Run& r, const void* x, long long M, int ldx, const h
         const long long wsb = hs_colsum_ws_bytes(M, lin.out_f);
         void* w = r.ws.alloc(wsb);
         CALL(r, colsum_rows(r.dt, dy, M, lin.out_f, ldy, lin.db, w, wsb, 0, r.pk_inv, r.s));
-        if (r.plan ? !overlap_enabled() : !r.side) r.ws.release(mk);
+        if (r.plan ? !sw::overlap() : !r.side) r.ws.release(mk);
     }
     return HS_OK;
 }
@@ -690,49 +601,14 @@ static int wgrad_defer_run(Run& r, const std::vector<DeferredWgrad>& items, long
 // The same gradients from TRANSPOSED operands (bf16): dyT [out][M] and xT [in][M] are both K-contiguous along the token
 // dimension, so dW = dyT . xT^T runs on the ds_read_b128 operand path (measured 1.5-1.7x the [k][row] "tn" form on
 // BERT-base shapes, tools/gemm_sweep.py).  The bias gradient is the row sums of dyT (one extra MFMA per fragment).
-static int g_wgrad_nt = -1;                  // -1: HAMSPINE_WGRAD_NT from the environment (default on); hs_set_wgrad_nt overrides
-static bool wgrad_nt_enabled() {             // off: weight gradients from the row-major operands ("tn")
-    if (g_wgrad_nt < 0) {
-        const char* e = getenv("HAMSPINE_WGRAD_NT");
-        g_wgrad_nt = (e && e[0] == '0') ? 0 : 1;
-    }
-    return g_wgrad_nt == 1;
-}
-// Packed text tower: the grouped weight gradients walk only the 32-token chunks that hold a valid token (Run::kc_on).
-static int g_bert_wgrad_chunks = -1;         // -1: HAMSPINE_BERT_WGRAD_CHUNKS from the environment (default on); hs_set_bert_wgrad_chunks overrides
-static bool bert_wgrad_chunks_enabled() {    // off: every padded column, as the padded tower
-    if (g_bert_wgrad_chunks < 0) {
-        const char* e = getenv("HAMSPINE_BERT_WGRAD_CHUNKS");
-        g_bert_wgrad_chunks = (e && e[0] == '0') ? 0 : 1;
-    }
-    return g_bert_wgrad_chunks == 1;
-}
-static bool grouped_bert_wgrad_enabled() {   // HAMSPINE_GROUPED_BERT_WGRAD=0: every weight-gradient GEMM of a BertLayer on its own
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("HAMSPINE_GROUPED_BERT_WGRAD");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-static bool dgrad_nt_enabled() {          // HAMSPINE_DGRAD_NT=0: BERT data gradients read the row-contiguous weights
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("HAMSPINE_DGRAD_NT");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-static bool deferred_transposes_enabled() {     // HAMSPINE_DEFER_TRANSPOSES=0: one launch per dY^T where the gradient appears
-    static const bool on = [] { const char* e = getenv("HAMSPINE_DEFER_TRANSPOSES"); return !(e && e[0] == '0'); }();
-    return on;
-}
+// (sw::wgrad_nt, HAMSPINE_WGRAD_NT / hs_set_wgrad_nt; off: the row-major "tn" form.)  Packed text tower: the grouped weight
+// gradients walk only the 32-token chunks that hold a valid token (Run::kc_on; sw::bert_wgrad_chunks).
 // tokens: the rows of src are tokens (packed rows: gathered to their padded columns, zeros at masked positions)
 static int transpose_run(Run& r, const void* src, void* dst, long long R, int Cc, int ld_src, bool for_grouped_wgrad = false,
                          bool tokens = false) {
     // (chunk-compacted only for the layer's own weight-gradient readers, which carry the count: Run::kc_on)
     const unsigned char tok = (tokens && r.pk_T) ? ((for_grouped_wgrad && r.kc_on) ? 2 : 1) : 0;
-    if (for_grouped_wgrad && r.tower_grp && r.group_nt && !r.plan && deferred_transposes_enabled()) {       // its reader is the tower's grouped grid: see pend_tr
+    if (for_grouped_wgrad && r.tower_grp && r.group_nt && !r.plan && sw::defer_transposes()) {       // its reader is the tower's grouped grid: see pend_tr
         r.pend_tr.push_back(Run::PendTr{src, dst, (int)R, Cc, ld_src, tok});
         return HS_OK;
     }
@@ -784,7 +660,7 @@ static int linear_wgrad_nt_run(Run& r, const void* xT, const void* dyT, long lon
         p.D_seg[0] = dw_seg[0];
         p.D_seg[1] = dw_seg[1];
     }
-    if (db && (r.group_nt || hs_gemm_suggest_split(out_f, in_f, (int)M, r.dt) <= 1) && fused_bias_grad_enabled()) {
+    if (db && (r.group_nt || hs_gemm_suggest_split(out_f, in_f, (int)M, r.dt) <= 1) && sw::fused_bias_grad()) {
         p.rowsum_a = db;
         if (seg_rows > 0) {
             p.rowsum_seg[0] = db_seg[0];
@@ -792,10 +668,10 @@ static int linear_wgrad_nt_run(Run& r, const void* xT, const void* dyT, long lon
         }
     }
     if (r.group_nt) {                    // no split-K inside a grouped grid: the group fills the chip
-        if (!r.plan && !(knock() & 2)) HS_PROPAGATE(gemm_group_add(r.grp_nt, &p, r.s, k_cols));
+        if (!r.plan && !(sw::knockout() & 2)) HS_PROPAGATE(gemm_group_add(r.grp_nt, &p, r.s, k_cols));
         return HS_OK;
     }
-    if (!r.plan && (knock() & 2)) { const int sp = hs_gemm_suggest_split(p.M, p.N, p.K, p.dtype); p.split_k = sp; if (sp > 1) (void)r.ws.alloc(hs_gemm_splitk_ws_bytes(&p)); return HS_OK; }
+    if (!r.plan && (sw::knockout() & 2)) { const int sp = hs_gemm_suggest_split(p.M, p.N, p.K, p.dtype); p.split_k = sp; if (sp > 1) (void)r.ws.alloc(hs_gemm_splitk_ws_bytes(&p)); return HS_OK; }
     return gemm_splitk(r, p);
 }
 // dx = dy W (* multiplier) (+ residual)
@@ -812,7 +688,7 @@ static int linear_dgrad_run(Run& r, const hs_linear& lin, const void* w_c, const
     p.b_elems = (long long)lin.out_f * lin.in_f;
     p.lda = ldy; p.ldb = lin.in_f;
     long long mk = -1;
-    if (!w_t && r.dt == HS_BF16 && dgrad_nt_enabled() && lin.out_f >= 1536 && M >= 2048 && lin.in_f % 8 == 0 && lin.out_f % 8 == 0) {
+    if (!w_t && r.dt == HS_BF16 && sw::dgrad_nt() && lin.out_f >= 1536 && M >= 2048 && lin.in_f % 8 == 0 && lin.out_f % 8 == 0) {
         // long K (= out_f) under many rows: one small transpose of the weight copy buys the K-contiguous operand path
         // (ConvNeXt MLP 12544 x 512 x 2048: 73.6 us as "nn", 48.8 us as "nt")
         mk = r.ws.mark();
@@ -830,7 +706,7 @@ static int linear_dgrad_run(Run& r, const hs_linear& lin, const void* w_c, const
     p.residual = residual; p.ldr = lddx;
     p.m_rows = r.pk_T;
     CALLK(r, 1024, gemm_impl(&p, r.s));
-    if (mk >= 0 && (r.plan ? !overlap_enabled() : !r.side)) r.ws.release(mk);
+    if (mk >= 0 && (r.plan ? !sw::overlap() : !r.side)) r.ws.release(mk);
     return HS_OK;
 }
 
@@ -865,8 +741,7 @@ static bool is_pointwise(const ConvShape& s) { return s.R == 1 && s.stride == 1 
 // both settings in one process.  The exact-f32 mode always takes the full-size route.
 static bool ds_compact(int dt, const ConvShape& s) {
     if (dt != HS_BF16 || s.R != 1 || s.stride != 2 || s.pad != 0) return false;
-    const char* e = getenv("HAMSPINE_DS_COMPACT");
-    return !(e && e[0] == '0');
+    return sw::ds_compact();
 }
 // HAMSPINE_IMG_LEAN: four places where the bf16 image tower used to write a full-size tensor only for the next elementwise kernel
 // to read it back; a bit mask, 0 = the separate launches, 15 = all four.  Read per call like HAMSPINE_DS_COMPACT.  The parts are
@@ -879,44 +754,12 @@ enum {
     IMG_LEAN_STEM_BWD = 2,   // stem: BatchNorm backward gathers the max-pool gradient in registers, no full-size gradient map
     IMG_LEAN_DS_FWD = 4,     // downsample identity formed inside the block output's apply pass, not stored
     IMG_LEAN_DS_BWD = 8,     // last stage + downsample BatchNorm backward in one partial / final / apply, dres not stored
-    IMG_LEAN_DEFAULT = IMG_LEAN_STEM_FWD | IMG_LEAN_DS_FWD | IMG_LEAN_DS_BWD
+    IMG_LEAN_DEFAULT = IMG_LEAN_STEM_FWD | IMG_LEAN_DS_FWD | IMG_LEAN_DS_BWD     // the default stated in hs_switch.h
 };
+static_assert(IMG_LEAN_DEFAULT == 13, "hs_switch.h states HAMSPINE_IMG_LEAN's default as a number");
 static int img_lean(int dt) {
     if (dt != HS_BF16) return 0;
-    const char* e = getenv("HAMSPINE_IMG_LEAN");
-    return e ? (atoi(e) & 15) : IMG_LEAN_DEFAULT;
-}
-static bool fused_ln_bwd_enabled() {        // HAMSPINE_FUSED_LN_BWD=0: separate LayerNorm-backward / dropout / column-sum passes
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("HAMSPINE_FUSED_LN_BWD");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-static bool grouped_wgrad_enabled() {     // HAMSPINE_GROUPED_WGRAD=0: the tower backward launches every weight gradient on its own
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("HAMSPINE_GROUPED_WGRAD");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-static bool bn_mask_from_x_enabled() {     // HAMSPINE_BN_MASK_FROM_X=1: inner-stage BatchNorm backward recomputes the ReLU mask from the
-    static int v = -1;                     // convolution output instead of reading the saved activation (one read less per pass;
-    if (v < 0) {                           // measured neutral on C2: 11.68-11.72 vs 11.66-11.70 ms -- off by default)
-        const char* e = getenv("HAMSPINE_BN_MASK_FROM_X");
-        v = (e && e[0] == '1') ? 1 : 0;
-    }
-    return v == 1;
-}
-static bool fused_bn_stats_enabled() {     // HAMSPINE_FUSED_BN_STATS=0: BatchNorm makes its own statistics pass
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("HAMSPINE_FUSED_BN_STATS");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
+    return (int)sw::img_lean();
 }
 
 // stats (optional, bf16 mode): receives the (count, mean, M2) partials of y per row tile for the BatchNorm that follows;
@@ -927,21 +770,13 @@ struct FoldedBn {          // eval-mode BatchNorm folded into the convolution: y
     int relu = 0;
     const void* identity = nullptr;
 };
-static bool bn_finish_enabled() {     // HAMSPINE_BN_FINISH=0: BatchNorm finishes its statistics in its own launch
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("HAMSPINE_BN_FINISH");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
 // bn (optional, with stats): the BatchNorm that follows; when the launch can it finishes the statistics too (bn->stats_done)
 static int conv_fwd_run(Run& r, const ConvShape& s, const void* x, const void* w_c, void* y, float* stats = nullptr,
                         int* stat_rows = nullptr, const FoldedBn* fold = nullptr, hs_bn_params* bn = nullptr) {
     // optional: 1x1 convolutions of a training step through the streaming kernel (pw_stream.hip: persistent workgroups,
     // A-stationary row blocks, one partial statistics row per workgroup; the BatchNorm finishes them in its own small launch)
-    static const bool pw_on = [] { const char* e = getenv("HAMSPINE_PW_STREAM"); return e && e[0] == '1'; }();   // measured: a wash, off
-    if (pw_on && !fold && is_pointwise(s) && r.dt == HS_BF16 && stats && stat_rows && fused_bn_stats_enabled()) {
+    const bool pw_on = sw::pw_stream();   // measured: a wash, off
+    if (pw_on && !fold && is_pointwise(s) && r.dt == HS_BF16 && stats && stat_rows && sw::fused_bn_stats()) {
         const long long Mo = (long long)s.N * s.P * s.Q;
         const PwPlan pl = pw_stream_plan(Mo, s.Cout, s.Cin, true);
         if (pl.ok) {
@@ -984,12 +819,12 @@ static int conv_fwd_run(Run& r, const ConvShape& s, const void* x, const void* w
     }
     p.b_kind = HS_B_KC;
     if (stat_rows) *stat_rows = 0;
-    if (stats && stat_rows && fused_bn_stats_enabled()) {
+    if (stats && stat_rows && sw::fused_bn_stats()) {
         const int rows = gemm_stat_rows(&p);
         if (rows > 0) {
             p.colstats = stats;
             *stat_rows = rows;
-            if (bn && bn->training && bn_finish_enabled()) {
+            if (bn && bn->training && sw::bn_finish()) {
                 const int frows = gemm_bn_finish_rows(&p);
                 if (frows > 0 && bn->ws == (void*)stats && bn->ws_bytes >= (long long)frows * s.Cout * 3 * 4) {
                     p.bn_finish = bn;
@@ -1019,19 +854,7 @@ struct BnSums {
 // take 1.42 instead of 1.20 ms (+5.9 us each: write-through stores -> counter round trip -> the last workgroup's dependent
 // reads) and 32 bn_bwd_final launches (0.19 ms, 5.8 us each) go away: 14.18 vs 14.04 ms of kernels, 11.08 vs 11.08 ms per
 // overlapped step.  A per-layer reduction dependency costs ~6 us as a launch or as an in-launch tail.  OFF unless
-// HAMSPINE_BNB_FINISH=1.
-static bool bnb_finish_enabled() {
-    static const bool on = [] { const char* e = getenv("HAMSPINE_BNB_FINISH"); return e && e[0] == '1'; }();
-    return on;
-}
-static bool fused_bn_bwd_enabled() {        // HAMSPINE_FUSED_BN_BWD=0: BatchNorm backward makes its own partial-sum pass
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("HAMSPINE_FUSED_BN_BWD");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
+// HAMSPINE_BNB_FINISH=1 (sw::bnb_finish).
 // compact (with a 1x1 pad-0 stride-2 convolution): dx is the compact gradient [N][P][Q][Cin], one unsplit pointwise GEMM.
 // rg (optional): `residual` is such a compact gradient over this convolution's input grid.
 static int conv_dgrad_run(Run& r, const ConvShape& s, const void* dy, const void* w_c, void* dx, const void* residual,
@@ -1045,7 +868,7 @@ static int conv_dgrad_run(Run& r, const ConvShape& s, const void* dy, const void
         p.a_kind = HS_A_KC; p.lda = s.Cout;
         p.b_kind = HS_B_RC; p.ldb = s.Cin;
         p.D = dx; p.ldd = s.Cin;
-        if (!r.plan && (knock() & 512)) return HS_OK;
+        if (!r.plan && (sw::knockout() & 512)) return HS_OK;
         // not gemm_splitk: the full-size launch it replaces is unsplit, and a K split would change the order of the sums
         CALL(r, gemm_impl(&p, r.s));
         return HS_OK;
@@ -1065,8 +888,8 @@ static int conv_dgrad_run(Run& r, const ConvShape& s, const void* dy, const void
     // late layers: few output tiles under a long K (7x7 maps: 200 tiles x 72 K tiles) -- split-K, reduced inside the launch
     // with the full epilogue (the parity-ordered stride-2 walk has its own K schedule and stays whole)
     if (bnb && bnb->rows) *bnb->rows = 0;
-    if (!r.plan && (knock() & 512)) return HS_OK;
-    if (bnb && (!residual || bnb->y) && r.dt == HS_BF16 && s.stride == 1 && s.Cin % 8 == 0 && fused_bn_bwd_enabled() && !(knock() & 16)) {
+    if (!r.plan && (sw::knockout() & 512)) return HS_OK;
+    if (bnb && (!residual || bnb->y) && r.dt == HS_BF16 && s.stride == 1 && s.Cin % 8 == 0 && sw::fused_bn_bwd() && !(sw::knockout() & 16)) {
         p.split_k = hs_gemm_suggest_split(p.M, p.N, p.K, p.dtype);             // what gemm_splitk will choose
         hs_gemm_params probe = p;
         probe.bnb_x = bnb->c; probe.bnb_scale = bnb->scale; probe.bnb_shift = bnb->shift; probe.bnb_mean = bnb->mean;
@@ -1076,7 +899,7 @@ static int conv_dgrad_run(Run& r, const ConvShape& s, const void* dy, const void
         if (rows > 0 && ((long long)rows * s.Cin * 2 + 4ll * s.Cin) * 4 <= bnb->partials_cap) {
             p = probe;
             *bnb->rows = rows;
-            const int frows = (bnb->finish && bnb->done && bnb_finish_enabled()) ? gemm_bnb_finish_rows(&probe) : 0;
+            const int frows = (bnb->finish && bnb->done && sw::bnb_finish()) ? gemm_bnb_finish_rows(&probe) : 0;
             if (frows > 0 && ((long long)frows * s.Cin * 2 + 4ll * s.Cin) * 4 <= bnb->partials_cap) {
                 p.bnb_finish = bnb->finish;
                 *bnb->rows = frows;
@@ -1135,7 +958,7 @@ static const void* weight_c(Run& r, CastList& cl, const float* w, long long n) {
 }
 static int run_casts(Run& r, CastList& cl) {
     if (cl.count == 0 || r.plan) return HS_OK;
-    if (knock() & 64) return HS_OK;
+    if (sw::knockout() & 64) return HS_OK;
     return hs_cast_f32_to_bf16_multi(cl.count, cl.src, cl.dst, cl.n, r.s);
 }
 
@@ -1331,7 +1154,8 @@ static int resblock_bwd_run(Run& r, const hs_resblock_desc& d, const void* x, co
         q.dy = g_out; q.y = y_out; q.x = b.c;
         q.gamma = cb.gamma; q.save_mean = b.mean; q.save_invstd = b.invstd;
         q.dx = g_in_; q.dres = g_res;
-        if (relu && !g_res && bn_mask_from_x_enabled()) {     // inner stages: relu(bn(c)) with no residual -- the sign of the
+        // (HAMSPINE_BN_MASK_FROM_X=1; one read less per pass, measured neutral on C2: 11.68-11.72 vs 11.66-11.70 ms -- off)
+        if (relu && !g_res && sw::bn_mask_from_x()) {     // inner stages: relu(bn(c)) with no residual -- the sign of the
             q.y = nullptr;                                    // forward value is recomputed from c (one read less per pass)
             q.scale = b.scale;
             q.shift = b.shift;
@@ -1498,7 +1322,7 @@ static int stem_fwd_run(Run& r, const hs_stem_desc& d, const float* image, void*
         return HS_OK;
     }
     int srows = 0;
-    if (d.training && fused_bn_stats_enabled() && (srows = gemm_stat_rows(&p)) > 0) p.colstats = (float*)L.bn_ws;
+    if (d.training && sw::fused_bn_stats() && (srows = gemm_stat_rows(&p)) > 0) p.colstats = (float*)L.bn_ws;
     hs_bn_params bp;
     memset(&bp, 0, sizeof(bp));
     bp.dtype = r.dt; bp.C = cb.Cout; bp.M = Mo;
@@ -1510,7 +1334,7 @@ static int stem_fwd_run(Run& r, const hs_stem_desc& d, const float* image, void*
     bp.running_mean = cb.running_mean; bp.running_var = cb.running_var;
     bp.save_mean = L.mean; bp.save_invstd = L.invstd; bp.scale = L.scale; bp.shift = L.shift;
     bp.ws = L.bn_ws; bp.ws_bytes = L.bn_ws_bytes;
-    if (p.colstats && bn_finish_enabled()) {
+    if (p.colstats && sw::bn_finish()) {
         const int frows = gemm_bn_finish_rows(&p);
         if (frows > 0 && L.bn_ws_bytes >= (long long)frows * cb.Cout * 3 * 4) {
             p.bn_finish = &bp;
@@ -1712,7 +1536,7 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
 
     // ---- output LN + FFN ----
     // one pass: LayerNorm backward, the hidden-dropout mask of the dense output and that dense layer's bias gradient
-    const bool fuse_ln = fused_ln_bwd_enabled();
+    const bool fuse_ln = sw::fused_ln_bwd();
     const void* g2 = d.hidden_dropout > 0.f ? dd2 : dh2;
     hs_linear out_l_w = d.out_l;
     if (fuse_ln) {
@@ -1728,13 +1552,13 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
         else if (d.hidden_dropout > 0.f) CALL(r, hs_dropout(r.dt, dh2, dd2, M * Hd, d.hidden_dropout, d.seed * 8 + 3, r.s));
     }
     // bf16: weight gradients from transposed operands (see linear_wgrad_nt_run); tbuf holds the two transposes of one layer
-    const bool nt = r.dt == HS_BF16 && wgrad_nt_enabled() && M % 8 == 0 && Hd % 8 == 0 && I % 8 == 0;
+    const bool nt = r.dt == HS_BF16 && sw::wgrad_nt() && M % 8 == 0 && Hd % 8 == 0 && I % 8 == 0;
     HS_REQUIRE(!r.pk_T || nt, "bert_layer_bwd: packed rows need the transposed-operand weight gradients (bf16, HAMSPINE_WGRAD_NT on)");
     // grouped: the four GEMMs run together at the end of the layer, so each keeps its own dY^T
     // (only when the four outputs give the chip enough 256x128 tiles: BERT-base 216; a narrow model keeps separate launches)
     const long long big_tiles = (long long)ceil_div(3 * Hd, 256) * ceil_div(Hd, 128) + (long long)ceil_div(Hd, 256) * ceil_div(Hd, 128) +
                                 (long long)ceil_div(I, 256) * ceil_div(Hd, 128) + (long long)ceil_div(Hd, 256) * ceil_div(I, 128);
-    const bool grouped = nt && grouped_bert_wgrad_enabled() && !overlap_enabled() && big_tiles >= 128;
+    const bool grouped = nt && sw::grouped_bert_wgrad() && !sw::overlap() && big_tiles >= 128;
     char* tA = nt ? (char*)r.ws.alloc(M * (long long)std::max(3 * Hd, I) * 2) : nullptr;   // dY^T (one at a time; grouped: FFN1's)
     char* tA_ffn2 = grouped ? (char*)r.ws.alloc(M * (long long)Hd * 2) : tA;
     char* tA_ao = grouped ? (char*)r.ws.alloc(M * (long long)Hd * 2) : tA;
@@ -1752,7 +1576,7 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
     // queue refuses to launch a problem that carries the count on its own, so a padded-layout reader of a compacted operand,
     // or the reverse, cannot come about).  Launches through gemm_splitk keep the padded columns: their host-side K split is
     // part of the summation order.
-    r.kc_on = r.pk_T && r.pk_kcols && grouped && !r.plan && bert_wgrad_chunks_enabled() && gemm_group_takes_k_cols();
+    r.kc_on = r.pk_T && r.pk_kcols && grouped && !r.plan && sw::bert_wgrad_chunks() && gemm_group_takes_k_cols();
     const int* const k_cols = r.kc_on ? r.pk_kcols : nullptr;
     // X^T of the four saved activations the weight gradients read: all known when the layer's backward starts, so they are
     // transposed by ONE launch (together with the weight copies below) instead of one launch in front of each GEMM
@@ -1775,13 +1599,13 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
             return st;
         }
         HS_PROPAGATE(transpose_run(r, dy_rm, tAk, M, lin.out_f, ldy, true, true));
-        const bool fused_b = lin.db && (r.group_nt || hs_gemm_suggest_split(lin.out_f, in_f, (int)M, r.dt) <= 1) && fused_bias_grad_enabled();
+        const bool fused_b = lin.db && (r.group_nt || hs_gemm_suggest_split(lin.out_f, in_f, (int)M, r.dt) <= 1) && sw::fused_bias_grad();
         HS_PROPAGATE(linear_wgrad_nt_run(r, xT, tAk, M, in_f, lin.out_f, lin.dw, lin.db, 0, nullptr, nullptr, k_cols));
         if (lin.db && !fused_b) HS_PROPAGATE(bias_by_colsum(lin, dy_rm, ldy));
         return HS_OK;
     };
     // bf16: data gradients of the three wide Linears on transposed weight copies (K-contiguous B operand)
-    const bool dnt = r.dt == HS_BF16 && dgrad_nt_enabled() && Hd % 8 == 0 && I % 8 == 0;
+    const bool dnt = r.dt == HS_BF16 && sw::dgrad_nt() && Hd % 8 == 0 && I % 8 == 0;
     char* wo_t = dnt ? (char*)r.ws.alloc((long long)Hd * I * 2) : nullptr;
     char* wi_t = dnt ? (char*)r.ws.alloc((long long)Hd * I * 2) : nullptr;
     char* wqkv_t = dnt ? (char*)r.ws.alloc(3ll * Hd * Hd * 2) : nullptr;
@@ -1843,7 +1667,7 @@ static int bert_layer_bwd_run(Run& r, const hs_bert_layer_desc& d, const void* x
         if (fused && nt) {
             HS_PROPAGATE(transpose_run(r, dqkv, tA_qkv, M, 3 * Hd, 3 * Hd, true, true));
             const bool bias_too = d.q.db && d.k.db && d.v.db && (r.group_nt || hs_gemm_suggest_split(3 * Hd, Hd, (int)M, r.dt) <= 1) &&
-                                  fused_bias_grad_enabled();
+                                  sw::fused_bias_grad();
             float* dws[2] = {d.k.dw, d.v.dw};
             float* dbs[2] = {d.k.db, d.v.db};
             HS_PROPAGATE(linear_wgrad_nt_run(r, tX_x, tA_qkv, M, Hd, 3 * Hd, d.q.dw, bias_too ? d.q.db : nullptr, Hd, dws, dbs, k_cols));
@@ -1977,8 +1801,8 @@ static int resnet_bwd_run(Run& r, const hs_resnet_desc& d, const void* const* dy
     // bf16: the blocks' weight-gradient GEMMs are not launched where they occur but collected and run as two grouped grids
     // (1x1 / spatial filters) behind the data-gradient chain; the blocks' scratch is then kept to the end (HAMSPINE_GROUPED_WGRAD=0:
     // one launch per convolution, scratch released per block)
-    r.defer_wgrad = dt == HS_BF16 && grouped_wgrad_enabled() && !overlap_enabled();
-    static const bool staged_on = [] { const char* e = getenv("HAMSPINE_STAGED_WGRAD"); return !(e && e[0] == '0'); }();
+    r.defer_wgrad = dt == HS_BF16 && sw::grouped_wgrad() && !sw::overlap();
+    const bool staged_on = sw::staged_wgrad();
     const bool staged = r.defer_wgrad && !r.plan && g_ms.n > 0 && staged_on;
     int seg = 0;
     std::vector<const void*> seg_ptrs;
@@ -1999,8 +1823,7 @@ static int resnet_bwd_run(Run& r, const hs_resnet_desc& d, const void* const* dy
     }
     float* xs_buf[2] = {(float*)r.ws.alloc(xs_bytes), (float*)r.ws.alloc(xs_bytes)};
     OwnSums own_next;                 // sums of the block about to be processed, if the previous iteration produced them
-    const char* xb_env = getenv("HAMSPINE_XBLOCK_BN");       // read per call: tests compare both settings in one process
-    const int xblock = xb_env ? atoi(xb_env) : 1;
+    const int xblock = (int)sw::xblock_bn();                 // read per call: tests compare both settings in one process
     int xs_rows = 0, xs_done = 0;
     hs_bn_bwd_params xs_fin;
     for (int i = d.n_blocks - 1; i >= 0; --i) {
@@ -2028,7 +1851,7 @@ static int resnet_bwd_run(Run& r, const hs_resnet_desc& d, const void* const* dy
         // M >= 25088) it is bandwidth-bound inside a tiled GEMM (205 MB at 3.4 TB/s: 61 us against 30 + 23) -> size gate.
         // HAMSPINE_XBLOCK_BN=0 turns it off, =2 takes it on every eligible block.
         const bool xb_size = xblock >= 2 || lo.y_bytes[i] <= (16ll << 20);
-        if (xblock > 0 && xb_size && i > 0 && dt == HS_BF16 && !prev_tap && !r.plan && d.blocks[i].main[0].stride == 1 && fused_bn_bwd_enabled()) {
+        if (xblock > 0 && xb_size && i > 0 && dt == HS_BF16 && !prev_tap && !r.plan && d.blocks[i].main[0].stride == 1 && sw::fused_bn_bwd()) {
             const hs_resblock_desc& pb = d.blocks[i - 1];
             const long long keep_saved = r.saved.off, keep_ws = r.ws.mark();
             r.saved.off = lo.lay_off[i];
@@ -2206,7 +2029,7 @@ static int bert_bwd_run(Run& r, const hs_bert_desc& d, const int64_t* ids, const
     // GEMMs = 216 tiles of 256 x 256, one per CU, K = 4096: the phase-pipelined body's steady state -- alone a layer is 108
     // such tiles, or 216 of 256 x 128 on the generic body at half the rate).  The layers' transposed operands stay allocated
     // until the flush; HAMSPINE_WGRAD_LAYERS=1 flushes per layer (round 2 behaviour).
-    static const int span = [] { const char* e = getenv("HAMSPINE_WGRAD_LAYERS"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 8 ? v : 2; }();
+    const int span = (int)sw::wgrad_layers();
     int pending = 0;
     long long wm = 0;
     const void* gps[8][16];
@@ -2277,34 +2100,71 @@ static int bert_bwd_run(Run& r, const hs_bert_desc& d, const int64_t* ids, const
 
 using namespace hs;
 
-// run the layout in plan mode first and refuse to launch anything when an arena is too small
-#define PLAN_CHECK(what, dt, svb, wsb, RUNCALL)                                                        \
-    do {                                                                                               \
-        Run pl;                                                                                        \
-        run_init(pl, dt, true, nullptr, 0, nullptr, 0, nullptr);                                       \
-        Run& r = pl;                                                                                   \
-        HS_PROPAGATE(RUNCALL);                                                                         \
-        HS_REQUIRE(pl.saved.peak <= (svb) && pl.ws.peak <= (wsb),                                      \
-                   "%s: arena too small (saved %lld needed / %lld given, ws %lld needed / %lld given)", \
-                   what, pl.saved.peak, (long long)(svb), pl.ws.peak, (long long)(wsb));               \
-    } while (0)
-
-#define QUERY_BODY(DESC_DT, RUNCALL)                                   \
-    Run r;                                                             \
-    run_init(r, DESC_DT, true, nullptr, 0, nullptr, 0, nullptr);       \
-    int st = RUNCALL;                                                  \
-    if (st != HS_OK) return st;                                        \
-    if (saved_bytes) *saved_bytes = r.saved.peak;                      \
-    if (ws_bytes) *ws_bytes = r.ws.peak;                               \
+// One C entry point = the same body twice: in plan mode first, and nothing is launched when an arena is too small for what
+// the plan took; then for real.  (The composites' bodies test for overflow themselves before their first launch; the test
+// behind the real pass covers the towers, whose bodies do not.)
+template <typename Body>
+static int run_entry(const char* what, int dt, void* saved, long long saved_bytes, void* ws, long long ws_bytes, void* stream,
+                     Body body) {
+    Run pl(dt);
+    HS_PROPAGATE(body(pl));
+    HS_REQUIRE(pl.saved.peak <= saved_bytes && pl.ws.peak <= ws_bytes,
+               "%s: arena too small (saved %lld needed / %lld given, ws %lld needed / %lld given)", what, pl.saved.peak,
+               saved_bytes, pl.ws.peak, ws_bytes);
+    Run r(dt, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
+    HS_PROPAGATE(body(r));
+    RUN_CHECK_ARENAS(r, what);
     return HS_OK;
+}
+// A tower backward lays `saved` out as its forward did: the plan pass of a backward body plans the forward first, for the
+// layout, and asks of `saved` what the forward asks.
+template <typename Fwd>
+static int plan_fwd_for_bwd(Run& r, Fwd fwd) {
+    if (!r.plan) return HS_OK;
+    Run f(r.dt);
+    HS_PROPAGATE(fwd(f));
+    r.saved.peak = f.saved.peak;
+    return HS_OK;
+}
+
+// *_query: the forward planned as given and the backward planned on a copy of the descriptor in which every parameter gradient
+// is wanted (the trainable case is the larger one); the answer is the maxima.  tower: `saved` is reported as the forward takes it.
+static float g_wanted;       // stands for a gradient buffer in such a copy: a plan pass dereferences nothing
+static void want(float*& p) { if (!p) p = &g_wanted; }
+static void want_all_grads(hs_conv_bn& c) { want(c.dw); want(c.dgamma); want(c.dbeta); }
+static void want_all_grads(hs_stem_desc& d) { want_all_grads(d.cb); }
+static void want_all_grads(hs_resblock_desc& d) {
+    for (int j = 0; j < d.n_main; ++j) want_all_grads(d.main[j]);
+    if (d.has_ds) want_all_grads(d.ds);
+}
+static void want_all_grads(hs_bert_layer_desc& d) {
+    for (hs_linear* l : {&d.q, &d.k, &d.v, &d.ao, &d.inter_l, &d.out_l}) { want(l->dw); want(l->db); }
+}
+static void want_all_grads(hs_resnet_desc& d) {
+    want_all_grads(d.stem);
+    for (int i = 0; i < d.n_blocks; ++i) want_all_grads(d.blocks[i]);
+}
+static void want_all_grads(hs_bert_desc& d) {
+    for (int i = 0; i < d.n_layers; ++i) want_all_grads(d.layers[i]);
+    want(d.dword); want(d.dtype0);
+}
+template <typename Desc, typename Fwd, typename Bwd>
+static int query_fwd_bwd(int dt, const Desc& d, Fwd fwd, Bwd bwd, int64_t* saved_bytes, int64_t* ws_bytes, bool tower = false) {
+    Run f(dt), b(dt);
+    HS_PROPAGATE(fwd(f));
+    Desc dd = d;
+    want_all_grads(dd);
+    HS_PROPAGATE(bwd(b, dd));
+    if (saved_bytes) *saved_bytes = tower ? f.saved.peak : std::max(f.saved.peak, b.saved.peak);
+    if (ws_bytes) *ws_bytes = std::max(f.ws.peak, b.ws.peak);
+    return HS_OK;
+}
 
 extern "C" {
 
 hs_status hs_attention_query(const hs_attn_desc* d, int64_t* saved_bytes, int64_t* ws_bytes) {
     HS_REQUIRE(d, "attention_query: null desc");
-    // the backward needs the larger workspace; report max(fwd, bwd)
-    Run r;
-    run_init(r, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
+    Run r(d->dtype);             // the backward alone: it needs the larger workspace
     HS_PROPAGATE(attention_bwd_run(r, *d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
     if (saved_bytes) *saved_bytes = r.saved.peak;
     if (ws_bytes) *ws_bytes = r.ws.peak;
@@ -2313,121 +2173,74 @@ hs_status hs_attention_query(const hs_attn_desc* d, int64_t* saved_bytes, int64_
 hs_status hs_attention_fwd(const hs_attn_desc* d, const void* q, const void* k, const void* v, void* o, void* saved,
                            int64_t saved_bytes, void* ws, int64_t ws_bytes, void* stream) {
     HS_REQUIRE(d && q && k && v && o && saved && ws, "attention_fwd: null argument");
-    PLAN_CHECK("attention_fwd", d->dtype, saved_bytes, ws_bytes, attention_fwd_run(r, *d, q, k, v, o));
-    Run r;
-    run_init(r, d->dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    return attention_fwd_run(r, *d, q, k, v, o);
+    return run_entry("attention_fwd", d->dtype, saved, saved_bytes, ws, ws_bytes, stream,
+                     [&](Run& r) { return attention_fwd_run(r, *d, q, k, v, o); });
 }
 hs_status hs_attention_bwd(const hs_attn_desc* d, const void* q, const void* k, const void* v, const void* d_o, void* dq,
                            void* dk, void* dv, void* saved, int64_t saved_bytes, void* ws, int64_t ws_bytes,
                            void* stream) {
     HS_REQUIRE(d && q && k && v && d_o && dq && dk && dv && saved && ws, "attention_bwd: null argument");
-    PLAN_CHECK("attention_bwd", d->dtype, saved_bytes, ws_bytes, attention_bwd_run(r, *d, q, k, v, d_o, dq, dk, dv));
-    Run r;
-    run_init(r, d->dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    return attention_bwd_run(r, *d, q, k, v, d_o, dq, dk, dv);
+    return run_entry("attention_bwd", d->dtype, saved, saved_bytes, ws, ws_bytes, stream,
+                     [&](Run& r) { return attention_bwd_run(r, *d, q, k, v, d_o, dq, dk, dv); });
 }
 
 hs_status hs_resblock_query(const hs_resblock_desc* d, int64_t* saved_bytes, int64_t* ws_bytes) {
     HS_REQUIRE(d, "resblock_query: null desc");
-    Run r;
-    run_init(r, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
-    HS_PROPAGATE(resblock_fwd_run(r, *d, nullptr, nullptr));
-    const long long sv = r.saved.peak, w1 = r.ws.peak;
-    Run b;
-    run_init(b, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
     int dummy;
-    HS_PROPAGATE(resblock_bwd_run(b, *d, nullptr, nullptr, nullptr, &dummy));
-    if (saved_bytes) *saved_bytes = std::max(sv, b.saved.peak);
-    if (ws_bytes) *ws_bytes = std::max(w1, b.ws.peak);
-    return HS_OK;
+    return query_fwd_bwd(d->dtype, *d, [&](Run& r) { return resblock_fwd_run(r, *d, nullptr, nullptr); },
+                         // *d, not the copy: this query alone sizes the backward for the gradients the caller's descriptor wants
+                         [&](Run& r, const hs_resblock_desc&) { return resblock_bwd_run(r, *d, nullptr, nullptr, nullptr, &dummy); },
+                         saved_bytes, ws_bytes);
 }
 hs_status hs_resblock_fwd(const hs_resblock_desc* d, const void* x, void* y, void* saved, int64_t saved_bytes, void* ws,
                           int64_t ws_bytes, void* stream) {
     HS_REQUIRE(d && x && y && saved && ws, "resblock_fwd: null argument");
-    PLAN_CHECK("resblock_fwd", d->dtype, saved_bytes, ws_bytes, resblock_fwd_run(r, *d, x, y));
-    Run r;
-    run_init(r, d->dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    return resblock_fwd_run(r, *d, x, y);
+    return run_entry("resblock_fwd", d->dtype, saved, saved_bytes, ws, ws_bytes, stream,
+                     [&](Run& r) { return resblock_fwd_run(r, *d, x, y); });
 }
 hs_status hs_resblock_bwd(const hs_resblock_desc* d, const void* x, const void* y, const void* dy, void* dx, void* saved,
                           int64_t saved_bytes, void* ws, int64_t ws_bytes, void* stream) {
     HS_REQUIRE(d && x && y && dy && saved && ws, "resblock_bwd: null argument");
-    PLAN_CHECK("resblock_bwd", d->dtype, saved_bytes, ws_bytes, resblock_bwd_run(r, *d, x, y, dy, dx));
-    Run r;
-    run_init(r, d->dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    return resblock_bwd_run(r, *d, x, y, dy, dx);
+    return run_entry("resblock_bwd", d->dtype, saved, saved_bytes, ws, ws_bytes, stream,
+                     [&](Run& r) { return resblock_bwd_run(r, *d, x, y, dy, dx); });
 }
 
 hs_status hs_stem_query(const hs_stem_desc* d, int64_t* saved_bytes, int64_t* ws_bytes) {
     HS_REQUIRE(d, "stem_query: null desc");
-    Run r;
-    run_init(r, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
-    HS_PROPAGATE(stem_fwd_run(r, *d, nullptr, nullptr));
-    const long long sv = r.saved.peak, w1 = r.ws.peak;
-    Run b;
-    run_init(b, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
-    hs_stem_desc dd = *d;
-    float dummy;
-    if (!dd.cb.dw) dd.cb.dw = &dummy;   // size the workspace for the trainable case
-    HS_PROPAGATE(stem_bwd_run(b, dd, nullptr, nullptr));
-    if (saved_bytes) *saved_bytes = std::max(sv, b.saved.peak);
-    if (ws_bytes) *ws_bytes = std::max(w1, b.ws.peak);
-    return HS_OK;
+    return query_fwd_bwd(d->dtype, *d, [&](Run& r) { return stem_fwd_run(r, *d, nullptr, nullptr); },
+                         [&](Run& r, const hs_stem_desc& dd) { return stem_bwd_run(r, dd, nullptr, nullptr); }, saved_bytes, ws_bytes);
 }
 hs_status hs_stem_fwd(const hs_stem_desc* d, const float* image, void* y, void* saved, int64_t saved_bytes, void* ws,
                       int64_t ws_bytes, void* stream) {
     HS_REQUIRE(d && image && y && saved && ws, "stem_fwd: null argument");
-    PLAN_CHECK("stem_fwd", d->dtype, saved_bytes, ws_bytes, stem_fwd_run(r, *d, image, y));
-    Run r;
-    run_init(r, d->dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    return stem_fwd_run(r, *d, image, y);
+    return run_entry("stem_fwd", d->dtype, saved, saved_bytes, ws, ws_bytes, stream,
+                     [&](Run& r) { return stem_fwd_run(r, *d, image, y); });
 }
 hs_status hs_stem_bwd(const hs_stem_desc* d, const void* y, const void* dy, void* saved, int64_t saved_bytes, void* ws,
                       int64_t ws_bytes, void* stream) {
     HS_REQUIRE(d && dy && saved && ws, "stem_bwd: null argument");
-    PLAN_CHECK("stem_bwd", d->dtype, saved_bytes, ws_bytes, stem_bwd_run(r, *d, y, dy));
-    Run r;
-    run_init(r, d->dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    return stem_bwd_run(r, *d, y, dy);
+    return run_entry("stem_bwd", d->dtype, saved, saved_bytes, ws, ws_bytes, stream,
+                     [&](Run& r) { return stem_bwd_run(r, *d, y, dy); });
 }
 
 hs_status hs_bert_layer_query(const hs_bert_layer_desc* d, int64_t* saved_bytes, int64_t* ws_bytes) {
     HS_REQUIRE(d, "bert_layer_query: null desc");
-    Run r;
-    run_init(r, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
-    HS_PROPAGATE(bert_layer_fwd_run(r, *d, nullptr, nullptr));
-    const long long sv = r.saved.peak, w1 = r.ws.peak;
-    Run b;
-    run_init(b, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
-    hs_bert_layer_desc dd = *d;
-    float dummy;
-    hs_linear* ls[6] = {&dd.q, &dd.k, &dd.v, &dd.ao, &dd.inter_l, &dd.out_l};
-    for (auto* l : ls) {   // size the workspace for the trainable case
-        if (!l->dw) l->dw = &dummy;
-        if (!l->db) l->db = &dummy;
-    }
-    int dmy;
-    HS_PROPAGATE(bert_layer_bwd_run(b, dd, nullptr, nullptr, &dmy));
-    if (saved_bytes) *saved_bytes = std::max(sv, b.saved.peak);
-    if (ws_bytes) *ws_bytes = std::max(w1, b.ws.peak);
-    return HS_OK;
+    int dummy;
+    return query_fwd_bwd(d->dtype, *d, [&](Run& r) { return bert_layer_fwd_run(r, *d, nullptr, nullptr); },
+                         [&](Run& r, const hs_bert_layer_desc& dd) { return bert_layer_bwd_run(r, dd, nullptr, nullptr, &dummy); },
+                         saved_bytes, ws_bytes);
 }
 hs_status hs_bert_layer_fwd(const hs_bert_layer_desc* d, const void* x, void* y, void* saved, int64_t saved_bytes,
                             void* ws, int64_t ws_bytes, void* stream) {
     HS_REQUIRE(d && x && y && saved && ws, "bert_layer_fwd: null argument");
-    PLAN_CHECK("bert_layer_fwd", d->dtype, saved_bytes, ws_bytes, bert_layer_fwd_run(r, *d, x, y));
-    Run r;
-    run_init(r, d->dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    return bert_layer_fwd_run(r, *d, x, y);
+    return run_entry("bert_layer_fwd", d->dtype, saved, saved_bytes, ws, ws_bytes, stream,
+                     [&](Run& r) { return bert_layer_fwd_run(r, *d, x, y); });
 }
 hs_status hs_bert_layer_bwd(const hs_bert_layer_desc* d, const void* x, const void* dy, void* dx, void* saved,
                             int64_t saved_bytes, void* ws, int64_t ws_bytes, void* stream) {
     HS_REQUIRE(d && x && dy && saved && ws, "bert_layer_bwd: null argument");
-    PLAN_CHECK("bert_layer_bwd", d->dtype, saved_bytes, ws_bytes, bert_layer_bwd_run(r, *d, x, dy, dx));
-    Run r;
-    run_init(r, d->dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    return bert_layer_bwd_run(r, *d, x, dy, dx);
+    return run_entry("bert_layer_bwd", d->dtype, saved, saved_bytes, ws, ws_bytes, stream,
+                     [&](Run& r) { return bert_layer_bwd_run(r, *d, x, dy, dx); });
 }
 
 hs_status hs_linear_fwd(int32_t dtype, const void* x, int64_t M, int32_t ldx, const hs_linear* lin, const void* w_lp,
@@ -2435,8 +2248,7 @@ hs_status hs_linear_fwd(int32_t dtype, const void* x, int64_t M, int32_t ldx, co
                         int32_t ldr, float dropout_p, uint64_t seed, void* stream) {
     HS_REQUIRE(x && lin && y && lin->w, "linear_fwd: null argument");
     HS_REQUIRE(dtype == HS_F32 || w_lp, "linear_fwd: bf16 mode needs the bf16 weight copy");
-    Run r;
-    run_init(r, dtype, false, nullptr, 0, nullptr, 0, (hipStream_t)stream);
+    Run r(dtype, nullptr, 0, nullptr, 0, (hipStream_t)stream);
     return linear_fwd_run(r, x, M, ldx, *lin, dtype == HS_F32 ? (const void*)lin->w : w_lp, y, ldy, out_dtype, act, preact,
                           residual, ldr, dropout_p, seed);
 }
@@ -2448,7 +2260,7 @@ hs_status hs_linear_bwd(int32_t dtype, const void* x, int64_t M, int32_t ldx, co
     HS_REQUIRE(dtype == HS_F32 || w_lp || !dx, "linear_bwd: bf16 mode needs the bf16 weight copy");
     // an open deferred set on this stream (hs_wgrad_defer_begin) takes the row-major weight / bias gradient: only the data
     // gradient is launched here
-    const bool deferred = (lin->dw || lin->db) && !overlap_enabled() && !linear_wgrad_takes_nt(dtype, M, ldx, *lin, ldy) &&
+    const bool deferred = (lin->dw || lin->db) && !sw::overlap() && !linear_wgrad_takes_nt(dtype, M, ldx, *lin, ldy) &&
                           wgrad_defer_has_room((hipStream_t)stream);
     auto both = [&](Run& r) -> int {
         if (!deferred) HS_PROPAGATE(linear_wgrad_run(r, x, M, ldx, *lin, dy, ldy));
@@ -2457,11 +2269,7 @@ hs_status hs_linear_bwd(int32_t dtype, const void* x, int64_t M, int32_t ldx, co
                                           mul_mode, mul_src, ldm, dx_residual));
         return HS_OK;
     };
-    PLAN_CHECK("linear_bwd", dtype, 0, ws_bytes, both(r));
-    Run r;
-    run_init(r, dtype, false, nullptr, 0, ws, ws_bytes, (hipStream_t)stream);
-    HS_PROPAGATE(both(r));
-    RUN_CHECK_ARENAS(r, "linear_bwd");
+    HS_PROPAGATE(run_entry("linear_bwd", dtype, nullptr, 0, ws, ws_bytes, stream, both));
     if (deferred) wgrad_defer_push((hipStream_t)stream, dtype, x, M, ldx, *lin, dy, ldy);
     return HS_OK;
 }
@@ -2494,8 +2302,7 @@ int64_t hs_wgrad_defer_ws_bytes(void* stream) {
         auto it = g_wd_open.find((hipStream_t)stream);
         if (it != g_wd_open.end()) items = it->second;
     }
-    Run r;
-    run_init(r, HS_BF16, true, nullptr, 0, nullptr, 0, nullptr);
+    Run r(HS_BF16);
     long long a = 0, b = 0, c = 0;
     if (wgrad_defer_run(r, items, &a, &b, &c) != HS_OK) return -1;
     return r.ws.peak + 1024;
@@ -2513,8 +2320,7 @@ hs_status hs_wgrad_defer_flush(void* stream, void* ws, int64_t ws_bytes) {
     }
     if (items.empty()) return HS_OK;
     HS_REQUIRE(ws != nullptr, "wgrad_defer_flush: null workspace");
-    Run r;
-    run_init(r, HS_BF16, false, nullptr, 0, ws, ws_bytes, s);
+    Run r(HS_BF16, nullptr, 0, ws, ws_bytes, s);
     long long gl = 0, cl = 0, up = 0;
     const int st = wgrad_defer_run(r, items, &gl, &cl, &up);
     if (st == HS_OK) g_wd_flushed.fetch_add((long long)items.size(), std::memory_order_relaxed);
@@ -2539,8 +2345,7 @@ void hs_wgrad_defer_counters(int64_t* out) {
 int64_t hs_linear_bwd_ws_bytes(int64_t M, int32_t in_f, int32_t out_f, int32_t dtype) {
     // a plan-mode pass of the code hs_linear_bwd runs (split-K slabs incl. group slabs, column-sum partials, the transposed
     // operand copies of the K-contiguous form), for dense rows (ldx = in_f, ldy = out_f) and both gradients wanted
-    Run r;
-    run_init(r, dtype, true, nullptr, 0, nullptr, 0, nullptr);
+    Run r(dtype);
     hs_linear lin;
     memset(&lin, 0, sizeof(lin));
     lin.in_f = in_f;
@@ -2612,24 +2417,14 @@ int64_t hs_abi_sizeof(int32_t which) {
 hs_status hs_resnet_query(const hs_resnet_desc* d, hs_resnet_plan* plan) {
     HS_REQUIRE(d && plan, "resnet_query: null argument");
     HS_PROPAGATE(resnet_check(*d));
-    Run r;
-    run_init(r, d->stem.dtype, true, nullptr, 0, nullptr, 0, nullptr);
     ResnetLayout lo;
-    HS_PROPAGATE(resnet_fwd_run(r, *d, nullptr, lo));
-    Run b;
-    run_init(b, d->stem.dtype, true, nullptr, 0, nullptr, 0, nullptr);
-    hs_resnet_desc dd = *d;           // size the workspace for the trainable case
-    float dummy;
-    auto need = [&](hs_conv_bn& c) { if (!c.dw) c.dw = &dummy; if (!c.dgamma) c.dgamma = &dummy; if (!c.dbeta) c.dbeta = &dummy; };
-    need(dd.stem.cb);
-    for (int i = 0; i < dd.n_blocks; ++i) {
-        for (int j = 0; j < dd.blocks[i].n_main; ++j) need(dd.blocks[i].main[j]);
-        if (dd.blocks[i].has_ds) need(dd.blocks[i].ds);
-    }
-    HS_PROPAGATE(resnet_bwd_run(b, dd, nullptr, lo));
+    int64_t saved_bytes, ws_bytes;
+    HS_PROPAGATE(query_fwd_bwd(d->stem.dtype, *d, [&](Run& r) { return resnet_fwd_run(r, *d, nullptr, lo); },
+                               [&](Run& r, const hs_resnet_desc& dd) { return resnet_bwd_run(r, dd, nullptr, lo); },
+                               &saved_bytes, &ws_bytes, true));
     memset(plan, 0, sizeof(*plan));
-    plan->saved_bytes = r.saved.peak;
-    plan->ws_bytes = std::max(r.ws.peak, b.ws.peak);
+    plan->saved_bytes = saved_bytes;
+    plan->ws_bytes = ws_bytes;
     for (int t = 0; t < d->n_taps; ++t) {
         const int i = d->tap_block[t];
         int C, H, W;
@@ -2644,41 +2439,18 @@ hs_status hs_resnet_fwd(const hs_resnet_desc* d, const float* image, void* saved
     HS_REQUIRE(d && image && saved && ws, "resnet_fwd: null argument");
     HS_PROPAGATE(resnet_check(*d));
     ResnetLayout lo;
-    {
-        Run pl;
-        run_init(pl, d->stem.dtype, true, nullptr, 0, nullptr, 0, nullptr);
-        HS_PROPAGATE(resnet_fwd_run(pl, *d, nullptr, lo));
-        HS_REQUIRE(pl.saved.peak <= saved_bytes && pl.ws.peak <= ws_bytes,
-                   "resnet_fwd: arena too small (saved %lld needed / %lld given, ws %lld needed / %lld given)", pl.saved.peak,
-                   (long long)saved_bytes, pl.ws.peak, (long long)ws_bytes);
-    }
-    Run r;
-    run_init(r, d->stem.dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    HS_PROPAGATE(resnet_fwd_run(r, *d, image, lo));
-    RUN_CHECK_ARENAS(r, "resnet_fwd");
-    return HS_OK;
+    return run_entry("resnet_fwd", d->stem.dtype, saved, saved_bytes, ws, ws_bytes, stream,
+                     [&](Run& r) { return resnet_fwd_run(r, *d, r.plan ? nullptr : image, lo); });
 }
 hs_status hs_resnet_bwd(const hs_resnet_desc* d, const void* const* dy_taps, void* saved, int64_t saved_bytes, void* ws,
                         int64_t ws_bytes, void* stream) {
     HS_REQUIRE(d && dy_taps && saved && ws, "resnet_bwd: null argument");
     HS_PROPAGATE(resnet_check(*d));
     ResnetLayout lo;
-    {
-        Run pl;
-        run_init(pl, d->stem.dtype, true, nullptr, 0, nullptr, 0, nullptr);
-        HS_PROPAGATE(resnet_fwd_run(pl, *d, nullptr, lo));
-        Run pb;
-        run_init(pb, d->stem.dtype, true, nullptr, 0, nullptr, 0, nullptr);
-        HS_PROPAGATE(resnet_bwd_run(pb, *d, nullptr, lo));
-        HS_REQUIRE(pl.saved.peak <= saved_bytes && pb.ws.peak <= ws_bytes,
-                   "resnet_bwd: arena too small (saved %lld needed / %lld given, ws %lld needed / %lld given)", pl.saved.peak,
-                   (long long)saved_bytes, pb.ws.peak, (long long)ws_bytes);
-    }
-    Run r;
-    run_init(r, d->stem.dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    HS_PROPAGATE(resnet_bwd_run(r, *d, dy_taps, lo));
-    RUN_CHECK_ARENAS(r, "resnet_bwd");
-    return HS_OK;
+    return run_entry("resnet_bwd", d->stem.dtype, saved, saved_bytes, ws, ws_bytes, stream, [&](Run& r) {
+        HS_PROPAGATE(plan_fwd_for_bwd(r, [&](Run& f) { return resnet_fwd_run(f, *d, nullptr, lo); }));
+        return resnet_bwd_run(r, *d, r.plan ? nullptr : dy_taps, lo);
+    });
 }
 
 /* test / analysis aid: where the post-activation buffers of the image tower live inside `saved` (every ReLU output and the
@@ -2688,15 +2460,13 @@ hs_status hs_resnet_bwd(const hs_resnet_desc* d, const void* const* dy_taps, voi
 int32_t hs_resnet_debug_offsets(const hs_resnet_desc* d, int64_t* out, int32_t max_entries) {
     if (!d || !out || resnet_check(*d) != HS_OK) return -1;
     char* const fake = (char*)(uintptr_t)0x100000;
-    Run r;
-    run_init(r, d->stem.dtype, true, nullptr, 0, nullptr, 0, nullptr);
+    Run r(d->stem.dtype);
     ResnetLayout lo;
     if (resnet_fwd_run(r, *d, nullptr, lo) != HS_OK) return -1;
     int n = 0;
     auto put = [&](long long off) { if (n < max_entries) out[n] = off; ++n; };
     {   // stem: replay its layout at its offset with a non-null base so that the pointers carry the offsets
-        Run q;
-        run_init(q, d->stem.dtype, false, fake, 1ll << 50, fake, 1ll << 50, nullptr);
+        Run q(d->stem.dtype, fake, 1ll << 50, fake, 1ll << 50, nullptr);
         q.saved.off = lo.lay_off[0];
         StemLayout L;
         if (stem_layout(q, d->stem, L) != HS_OK) return -1;
@@ -2704,8 +2474,7 @@ int32_t hs_resnet_debug_offsets(const hs_resnet_desc* d, int64_t* out, int32_t m
         put((char*)L.idx - fake);
     }
     for (int i = 0; i < d->n_blocks; ++i) {
-        Run q;
-        run_init(q, d->stem.dtype, false, fake, 1ll << 50, fake, 1ll << 50, nullptr);
+        Run q(d->stem.dtype, fake, 1ll << 50, fake, 1ll << 50, nullptr);
         q.saved.off = lo.lay_off[i + 1];
         ResLayout L;
         if (res_layout(q, d->blocks[i], L) != HS_OK) return -1;
@@ -2718,26 +2487,10 @@ int32_t hs_resnet_debug_offsets(const hs_resnet_desc* d, int64_t* out, int32_t m
 hs_status hs_bert_query(const hs_bert_desc* d, int64_t* saved_bytes, int64_t* ws_bytes, int64_t* out_offset) {
     HS_REQUIRE(d, "bert_query: null desc");
     HS_PROPAGATE(bert_check(*d));
-    Run r;
-    run_init(r, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
     BertTowerLayout lo;
-    HS_PROPAGATE(bert_fwd_run(r, *d, nullptr, nullptr, lo));
-    Run b;
-    run_init(b, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
-    hs_bert_desc dd = *d;
-    float dummy;
-    for (int i = 0; i < dd.n_layers; ++i) {
-        hs_linear* ls[6] = {&dd.layers[i].q, &dd.layers[i].k, &dd.layers[i].v, &dd.layers[i].ao, &dd.layers[i].inter_l, &dd.layers[i].out_l};
-        for (auto* l : ls) {
-            if (!l->dw) l->dw = &dummy;
-            if (!l->db) l->db = &dummy;
-        }
-    }
-    if (!dd.dword) dd.dword = &dummy;
-    if (!dd.dtype0) dd.dtype0 = &dummy;
-    HS_PROPAGATE(bert_bwd_run(b, dd, nullptr, nullptr, nullptr, lo));
-    if (saved_bytes) *saved_bytes = r.saved.peak;
-    if (ws_bytes) *ws_bytes = std::max(r.ws.peak, b.ws.peak);
+    HS_PROPAGATE(query_fwd_bwd(d->dtype, *d, [&](Run& r) { return bert_fwd_run(r, *d, nullptr, nullptr, lo); },
+                               [&](Run& r, const hs_bert_desc& dd) { return bert_bwd_run(r, dd, nullptr, nullptr, nullptr, lo); },
+                               saved_bytes, ws_bytes, true));
     if (out_offset) *out_offset = d->pack_rows ? lo.out_off : lo.y_off[d->n_layers];
     return HS_OK;
 }
@@ -2746,48 +2499,26 @@ hs_status hs_bert_fwd(const hs_bert_desc* d, const int64_t* ids, const int64_t* 
     HS_REQUIRE(d && ids && saved && ws, "bert_fwd: null argument");
     HS_PROPAGATE(bert_check(*d));
     BertTowerLayout lo;
-    {
-        Run pl;
-        run_init(pl, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
-        HS_PROPAGATE(bert_fwd_run(pl, *d, nullptr, nullptr, lo));
-        HS_REQUIRE(pl.saved.peak <= saved_bytes && pl.ws.peak <= ws_bytes,
-                   "bert_fwd: arena too small (saved %lld needed / %lld given, ws %lld needed / %lld given)", pl.saved.peak,
-                   (long long)saved_bytes, pl.ws.peak, (long long)ws_bytes);
-    }
-    Run r;
-    run_init(r, d->dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    HS_PROPAGATE(bert_fwd_run(r, *d, ids, mask, lo));
-    RUN_CHECK_ARENAS(r, "bert_fwd");
-    return HS_OK;
+    return run_entry("bert_fwd", d->dtype, saved, saved_bytes, ws, ws_bytes, stream, [&](Run& r) {
+        return r.plan ? bert_fwd_run(r, *d, nullptr, nullptr, lo) : bert_fwd_run(r, *d, ids, mask, lo);
+    });
 }
 hs_status hs_bert_bwd(const hs_bert_desc* d, const int64_t* ids, const int64_t* mask, const void* dy, void* saved,
                       int64_t saved_bytes, void* ws, int64_t ws_bytes, void* stream) {
     HS_REQUIRE(d && ids && dy && saved && ws, "bert_bwd: null argument");
     HS_PROPAGATE(bert_check(*d));
     BertTowerLayout lo;
-    {
-        Run pl;
-        run_init(pl, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
-        HS_PROPAGATE(bert_fwd_run(pl, *d, nullptr, nullptr, lo));
-        Run pb;
-        run_init(pb, d->dtype, true, nullptr, 0, nullptr, 0, nullptr);
-        HS_PROPAGATE(bert_bwd_run(pb, *d, nullptr, nullptr, nullptr, lo));
-        HS_REQUIRE(pl.saved.peak <= saved_bytes && pb.ws.peak <= ws_bytes,
-                   "bert_bwd: arena too small (saved %lld needed / %lld given, ws %lld needed / %lld given)", pl.saved.peak,
-                   (long long)saved_bytes, pb.ws.peak, (long long)ws_bytes);
-    }
-    Run r;
-    run_init(r, d->dtype, false, saved, saved_bytes, ws, ws_bytes, (hipStream_t)stream);
-    HS_PROPAGATE(bert_bwd_run(r, *d, ids, mask, dy, lo));
-    RUN_CHECK_ARENAS(r, "bert_bwd");
-    return HS_OK;
+    return run_entry("bert_bwd", d->dtype, saved, saved_bytes, ws, ws_bytes, stream, [&](Run& r) {
+        HS_PROPAGATE(plan_fwd_for_bwd(r, [&](Run& f) { return bert_fwd_run(f, *d, nullptr, nullptr, lo); }));
+        return r.plan ? bert_bwd_run(r, *d, nullptr, nullptr, nullptr, lo) : bert_bwd_run(r, *d, ids, mask, dy, lo);
+    });
 }
-/* weight-gradient side stream inside the composites: 1 on (default, or HAMSPINE_OVERLAP), 0 off (every kernel of a
-   composite on the caller's stream, e.g. to time kernels in isolation). */
-void hs_set_overlap(int32_t on) { hs::g_overlap = on ? 1 : 0; }
+/* weight-gradient side stream inside the composites: 1 on (or HAMSPINE_OVERLAP=1), 0 off (default: every kernel of a
+   composite on the caller's stream). */
+void hs_set_overlap(int32_t on) { hs::sw::set_overlap(on); }
 /* 1 when the switches this library latched leave the packed-row BERT tower (hs_bert_desc.pack_rows) its kernels: the
    transposed-operand weight gradients (HAMSPINE_WGRAD_NT / hs_set_wgrad_nt) and the fused attention (HAMSPINE_FUSED_ATTENTION). */
-int32_t hs_bert_pack_rows_available(void) { return (hs::wgrad_nt_enabled() && hs::fused_attention_enabled()) ? 1 : 0; }
+int32_t hs_bert_pack_rows_available(void) { return (hs::sw::wgrad_nt() && hs::sw::fused_attention()) ? 1 : 0; }
 hs_status hs_grad_milestones(int32_t n, const void* const* grad_ptrs, void* const* events) {
     HS_REQUIRE(n >= 0 && n <= kMaxMilestones, "grad_milestones: %d entries (max %d)", n, kMaxMilestones);
     HS_REQUIRE(n == 0 || (grad_ptrs && events), "grad_milestones: null argument");
@@ -2807,6 +2538,6 @@ int32_t hs_measure_build(void) {
 #endif
 }
 /* BertLayer weight gradients from transposed (K-contiguous) operands: 1 on (default), 0 = the row-major "tn" form. */
-void hs_set_wgrad_nt(int32_t on) { hs::g_wgrad_nt = on ? 1 : 0; }
-void hs_set_bert_wgrad_chunks(int32_t on) { hs::g_bert_wgrad_chunks = on ? 1 : 0; }
+void hs_set_wgrad_nt(int32_t on) { hs::sw::set_wgrad_nt(on); }
+void hs_set_bert_wgrad_chunks(int32_t on) { hs::sw::set_bert_wgrad_chunks(on); }
 }

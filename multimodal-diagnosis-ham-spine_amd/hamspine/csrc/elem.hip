@@ -3,7 +3,7 @@
 // 16-byte accesses wherever the layout allows, wave-shuffle reductions, no atomics except the
 // embedding scatter-add (duplicate token ids).
 #include <algorithm>
-#include "hs_common.h"
+#include "hs_internal.h"
 
 namespace hs {
 

@@ -9,6 +9,8 @@
 #include <tuple>
 #include "gemm_launch.h"
 #include "gemm_p8.h"
+#include "hs_internal.h"
+#include "hs_switch.h"
 
 namespace hs {
 
@@ -103,10 +105,6 @@ static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 static bool batch_is_one(const hs_gemm_params* p) { return p->batch <= 1; }
 // the phase-pipelined body (gemm_p8.h) for the shapes it wins on; HAMSPINE_P8=0 keeps every GEMM on the generic body
-static bool p8_enabled() {
-    static const bool on = [] { const char* e = getenv("HAMSPINE_P8"); return !(e && e[0] == '0'); }();
-    return on;
-}
 static int p8_cfg(const hs_gemm_params* p) {
     // 256 x 256 tiles where they give the chip enough workgroups (BERT-base at 4096 tokens: N = 2304 / 3072 -> 144 / 192)
     if (p->M % 256 == 0 && p->N % 256 == 0 && (long long)(p->M / 256) * (p->N / 256) >= 128) return CFG_P8_256;
@@ -136,12 +134,8 @@ static int auto_cfg(const hs_gemm_params* p, bool vec) {
 // The 3x3 halo-patch kernel (conv3.hip) takes stride-1 pad-1 3x3 forward convolutions in standard NHWC with a plain bf16
 // epilogue (optionally the BatchNorm statistics riders): tile = R whole image rows (R * W <= 112 pixels) x 64 channels.
 // HAMSPINE_CONV3=0 keeps them on the generic implicit GEMM.
-static bool conv3_enabled() {
-    static const bool on = [] { const char* e = getenv("HAMSPINE_CONV3"); return !(e && e[0] == '0'); }();
-    return on;
-}
 static bool conv3_plan(const hs_gemm_params* p, int* rows, int* tpi, int* fm) {
-    if (!conv3_enabled() || g_dbg_cfg >= 0) return false;
+    if (!sw::conv3() || g_dbg_cfg >= 0) return false;
     const hs_conv_geom& g = p->g;
     if (p->dtype != HS_BF16 || p->a_kind != HS_A_CONV || p->b_kind != HS_B_KC || p->split_k > 1 || p->batch > 1) return false;
     if (g.R != 3 || g.S != 3 || g.stride != 1 || g.pad != 1 || g.P != g.H || g.Q != g.W || g.C % 64 != 0 || p->N % 64 != 0) return false;
@@ -178,7 +172,6 @@ static bool bn_finish_variant(int cfg, int combo) {
     return (combo == 0 && (cfg == CFG_64x64 || cfg == CFG_128x64)) || (combo == 3 && (cfg == CFG_64x64 || cfg == CFG_128x64 || cfg == CFG_STEM || cfg == CFG_C3));
 }
 
-static int g_pack_spread = -1;       // packed-row launches: live tiles dealt over all XCDs (gemm_prepare); -1: from the environment
 // everything gemm_impl decides before the launch
 struct Prepared {
     GemmArgs a;
@@ -310,12 +303,7 @@ static int gemm_prepare(const hs_gemm_params* p, hipStream_t stream, Prepared& q
             a.div_mw = make_fastdiv(g.W);
             // stride 2: parity-major row order lets the kernel skip the 3/4 of the filter taps that cannot reach a given
             // input pixel (HAMSPINE_PARITY_DGRAD=0 keeps the natural order)
-            static int parity_on = -1;
-            if (parity_on < 0) {
-                const char* e = getenv("HAMSPINE_PARITY_DGRAD");
-                parity_on = (e && e[0] == '0') ? 0 : 1;
-            }
-            if (parity_on && bf16 && g.stride == 2 && g.H % 2 == 0 && g.W % 2 == 0 && g.R * g.S <= 15 && split == 1 && batch == 1 &&
+            if (sw::parity_dgrad() && bf16 && g.stride == 2 && g.H % 2 == 0 && g.W % 2 == 0 && g.R * g.S <= 15 && split == 1 && batch == 1 &&
                 !p->seg_rows && !p->colstats && !p->bnb_partials) {
                 a.parity = 1;
                 a.quarter = g.N * (g.H / 2) * (g.W / 2);
@@ -399,7 +387,7 @@ static int gemm_prepare(const hs_gemm_params* p, hipStream_t stream, Prepared& q
         };
         int want = -1;
         if (g_dbg_cfg >= CFG_P8_256 && g_dbg_cfg <= CFG_P8_128) want = g_dbg_cfg;
-        else if (g_dbg_cfg < 0 && p8_enabled()) want = p8_cfg(p);
+        else if (g_dbg_cfg < 0 && sw::p8()) want = p8_cfg(p);
         if (p8_ok && want >= 0 && fits(want)) cfg = want;
     }
     if (force_cfg < 0 && combo == 3 && conv3_plan(p, &a.c3_rows, &a.c3_tpi, &a.c3_fm)) cfg = CFG_C3;
@@ -480,8 +468,7 @@ static int gemm_prepare(const hs_gemm_params* p, hipStream_t stream, Prepared& q
         HS_REQUIRE(a.bnf_tickets != nullptr, "hs_gemm: cannot allocate the arrival counters");
     }
     {   // measurement aid (HAMSPINE_EPI_HIST=1): which epilogue feature sets the launches use, printed at exit
-        static const bool hist = [] { const char* e = getenv("HAMSPINE_EPI_HIST"); return e && e[0] == '1'; }();
-        if (hist) {
+        if (sw::epi_hist()) {
             static std::mutex mu;
             static std::map<std::pair<unsigned, int>, long long> cnt;
             static const bool reg = [] {
@@ -514,11 +501,8 @@ static int gemm_prepare(const hs_gemm_params* p, hipStream_t stream, Prepared& q
     if (a.m_rows) {
         // packed rows: deal the workgroups over the live tile rows only (tile_from_block).  Unsplit launches without statistics
         // riders or stamps: there nothing but the tile coordinates depends on the workgroup index.
-        if (g_pack_spread < 0) {        // HAMSPINE_PACK_XCD_SPREAD=0 / hs_set_pack_xcd_spread(0): off
-            const char* e = getenv("HAMSPINE_PACK_XCD_SPREAD");
-            g_pack_spread = (e && e[0] == '0') ? 0 : 1;
-        }
-        a.pack_spread = (g_pack_spread == 1 && split == 1 && !a.colstats && !a.bnb_partials && !a.stamps && cfg != CFG_C3) ? 1 : 0;
+        // (HAMSPINE_PACK_XCD_SPREAD=0 / hs_set_pack_xcd_spread(0): off)
+        a.pack_spread = (sw::pack_xcd_spread() && split == 1 && !a.colstats && !a.bnb_partials && !a.stamps && cfg != CFG_C3) ? 1 : 0;
     }
     dim3 grid(a.tiles_m * a.tiles_n, 1, split > 1 ? split : batch);
     {   // persistent launch: more tiles than workgroups the chip holds at once -> one workgroup per resident slot walks
@@ -527,7 +511,7 @@ static int gemm_prepare(const hs_gemm_params* p, hipStream_t stream, Prepared& q
         // registers leave room for 2 instead of 3-5 workgroups per CU and those layers live on bytes in flight): the
         // hardware already overlaps one workgroup's set-up with its neighbours' epilogues.  OFF unless HAMSPINE_PERSISTENT=1
         // (or hs_gemm_debug ablation bit 64).
-        static const bool on = [] { const char* e = getenv("HAMSPINE_PERSISTENT"); return e && e[0] == '1'; }();
+        const bool on = sw::persistent();
         static const int cus = [] { hipDeviceProp_t pr; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 256; }();
         if ((on || (g_dbg_ablate & 64)) && bf16 && split == 1 && batch == 1 && !a.stamps && !a.m_rows && !a.drop_rows && !p->rowsum_a && !p->bnb_partials && !p->bn_finish && (cfg == CFG_64x64 || cfg == CFG_128x64) &&
             (combo == 0 || combo == 1 || combo == 3 || combo == 4)) {
@@ -595,7 +579,7 @@ int gemm_bnb_finish_rows(const hs_gemm_params* p) {
 }
 
 // rg (optional, internal callers only): the residual is compact, see ResGather
-int gemm_impl(const hs_gemm_params* p, hipStream_t stream, const ResGather* rg = nullptr) {
+int gemm_impl(const hs_gemm_params* p, hipStream_t stream, const ResGather* rg) {
     Prepared q;
     HS_PROPAGATE(gemm_prepare(p, stream, q, -1, rg));
     const GemmArgs& a = q.a;
@@ -706,8 +690,7 @@ int gemm_group_flush(GemmGroup* g, hipStream_t s) {
     memcpy(host.data() + kHead, g->items.data(), (size_t)n * sizeof(GemmArgs));
     if (host != g->shadow) {
         // rare (first step, or an arena moved): the previous launch of this group may still be reading the table
-        static const bool dbg = [] { const char* e = getenv("HAMSPINE_GROUP_DEBUG"); return e && e[0] == '1'; }();
-        if (dbg) {
+        if (sw::group_debug()) {
             size_t diff = 0;
             for (size_t i = 0; i < std::min(host.size(), g->shadow.size()); ++i) diff += host[i] != g->shadow[i];
             fprintf(stderr, "[group] table upload: %d problems, %zu bytes (%zu before), %zu bytes differ\n", n, bytes, g->shadow.size(), diff);
@@ -794,7 +777,7 @@ int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s, const i
     const bool big = p->a_kind == HS_A_KC && p->b_kind == HS_B_KC;       // K-contiguous weight gradients: 256x128 tiles
     // ... or, when every tile is a full 256 x 256 one and the group is a deep-K one (K >= 2048: the K walk has to amortise the
     // one-tile-per-CU body's ramp), the phase-pipelined body.  HAMSPINE_P8_WGRAD=0 keeps the generic 256x128 tiles.
-    static const bool p8w = [] { const char* e = getenv("HAMSPINE_P8_WGRAD"); return !(e && e[0] == '0'); }();
+    const bool p8w = sw::p8_wgrad();
     const bool want_p8 = big && p8w && p->dtype == HS_BF16 && p->M % 256 == 0 && p->N % 256 == 0 && p->K % 64 == 0 && p->K >= 2048 &&
                          (p->batch <= 1) && p->split_k <= 1 && g_dbg_cfg < 0 && (g->items.empty() || g->combo != 0 || g->cfg == CFG_P8_256);
     HS_PROPAGATE(gemm_prepare(p, s, q, big ? (want_p8 ? CFG_P8_256 : CFG_256x128) : -1));
@@ -839,7 +822,7 @@ int gemm_group_add(GemmGroup* g, const hs_gemm_params* p, hipStream_t s, const i
 extern "C" {
 /* measurement only: device buffer of 6 x (workgroups of the largest launch) uint64, or NULL to switch the stamps off */
 void hs_gemm_debug_stamps(void* device_buffer) { hs::g_dbg_stamps = (unsigned long long*)device_buffer; }
-void hs_set_pack_xcd_spread(int32_t on) { hs::g_pack_spread = on ? 1 : 0; }
+void hs_set_pack_xcd_spread(int32_t on) { hs::sw::set_pack_xcd_spread(on); }
 int64_t hs_gemm_k_cols_queued(void) { return hs::g_k_cols_queued.load(std::memory_order_relaxed); }
 void hs_gemm_debug(int32_t cfg_override, int32_t ablate) {
     hs::g_dbg_cfg = cfg_override;
@@ -938,19 +921,11 @@ int32_t hs_gemm_suggest_split(int32_t M, int32_t N, int32_t K, int32_t dtype) {
     const long long tiles = (long long)hs::ceil_div(M, 64) * hs::ceil_div(N, 64);
     const int ktiles = hs::ceil_div(K, bk);
     if (tiles >= 256 || ktiles < 16) return 1;
-    static const long long units = [] {          // measurement: HAMSPINE_SPLIT_UNITS overrides the target number of workgroups
-        const char* e = getenv("HAMSPINE_SPLIT_UNITS");
-        const long long v = e ? atoll(e) : 0;
-        return v > 0 ? v : 512ll;
-    }();
+    const long long units = hs::sw::split_units();   // measurement: HAMSPINE_SPLIT_UNITS overrides the target number of workgroups
     long long s = (units + tiles - 1) / tiles;   // 256/384/768 work units measured the same on C2 with the separate reduce pass
     const long long smax = ktiles / 8 > 0 ? ktiles / 8 : 1;   // keep >= 8 k-tiles per split
     if (s > smax) s = smax;
-    static const long long cap = [] {            // measurement: HAMSPINE_SPLIT_MAX overrides the largest split
-        const char* e = getenv("HAMSPINE_SPLIT_MAX");
-        const long long v = e ? atoll(e) : 0;
-        return v > 0 ? v : 64ll;
-    }();
+    const long long cap = hs::sw::split_max();       // measurement: HAMSPINE_SPLIT_MAX overrides the largest split
     if (s > cap) s = cap;
     return (int32_t)(s < 1 ? 1 : s);
 }

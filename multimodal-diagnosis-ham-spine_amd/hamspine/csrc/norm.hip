@@ -6,7 +6,7 @@
 // transformers BertEmbeddings / BertSelfOutput / BertOutput LayerNorm, eps 1e-12).
 #include <algorithm>
 #include <type_traits>
-#include "hs_common.h"
+#include "hs_internal.h"
 
 namespace hs {
 

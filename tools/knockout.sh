@@ -1,6 +1,6 @@
 #!/bin/bash
 # Marginal cost of each class of launches in the OVERLAPPED C2 step: the step time with the class left out (HAMSPINE_KNOCKOUT,
-# csrc/blocks.hip knock(); results are garbage in those runs) against the full step.   bash tools/knockout.sh > table.txt
+# csrc/hs_switch.h sw::knockout(); results are garbage in those runs) against the full step.   bash tools/knockout.sh > table.txt
 # The switch is compiled in only with -DHS_MEASURE, and bench.py refuses such a build / the variable, so this script rebuilds
 # the library that way, times the step with tools/step_time.py (prints ms/step only, never a bench line) and restores the
 # release build at the end.
