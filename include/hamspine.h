@@ -293,14 +293,21 @@ int64_t hs_layernorm_bwd_ws_bytes(int64_t M, int32_t H);
 #define HS_CAST_MAX 48
 #define HS_ADAM_MAX 32
 
-/* MaxPool2d(k, s, p) on NHWC; idx (uint8, same shape as y) keeps the arg-max tap for the backward.
-   Replaces torchvision ResNet.maxpool (reference encoder.py:67). */
+/* MaxPool2d(k, s, p) on NHWC; idx (uint8, same shape as y) keeps the arg-max tap r * k + s for the backward: the first
+   maximum in (r, s) scan order, taps in the padding never win (they count as -inf).  The backward is a gather.
+   Replaces torchvision ResNet.maxpool (reference encoder.py:67).
+   Preconditions, refused before any arithmetic or launch: C % 4 == 0 (f32) / C % 8 == 0 (bf16) and ksize <= 15 (HS_ERR_ARG);
+   N, H, W, C >= 1, ksize >= 1, stride >= 1, pad >= 0, H + 2 pad >= ksize and W + 2 pad >= ksize, so that P, Q >= 1
+   (HS_ERR_UNSUPPORTED).  pad <= ksize / 2
+   as torch demands is not checked: a window that lies in the padding altogether yields -inf and tap 0. */
 hs_status hs_maxpool_fwd(int32_t dtype, const void* x, void* y, void* idx, int32_t N, int32_t H, int32_t W, int32_t C,
                          int32_t ksize, int32_t stride, int32_t pad, void* stream);
 hs_status hs_maxpool_bwd(int32_t dtype, const void* dy, const void* idx, void* dx, int32_t N, int32_t H, int32_t W,
                          int32_t C, int32_t ksize, int32_t stride, int32_t pad, void* stream);
 /* y[b][:] = mean_t x[b][t][:]  (AdaptiveAvgPool / tokens.mean(dim=1); reference
-   modules/fusion_blocks.py:97-98,170-178, model.py:283-290, torchvision ResNet.avgpool). */
+   modules/fusion_blocks.py:97-98,170-178, model.py:283-290, torchvision ResNet.avgpool).  The sum is multiplied by
+   float(1 / Nt); the backward is dx[b][t][:] = dy[b][:] * float(1 / Nt), rounded once.  B, Nt >= 1 and H % 4 == 0 (f32) /
+   H % 8 == 0 (bf16), refused otherwise.  out_f32 / dy_f32: y / dy is float32 whatever dtype says. */
 hs_status hs_mean_tokens_fwd(int32_t dtype, const void* x, void* y, int32_t B, int32_t Nt, int32_t H, int32_t out_f32,
                              void* stream);
 hs_status hs_mean_tokens_bwd(int32_t dtype, const void* dy, void* dx, int32_t B, int32_t Nt, int32_t H, int32_t dy_f32,
@@ -342,6 +349,7 @@ hs_status hs_axpby(int32_t in_dtype, int32_t out_dtype, const void* x, const voi
                    float b, void* stream);
 /* out[i] = x[i] * keep(seed, i) / (1-p): the same call is its own backward. */
 hs_status hs_dropout(int32_t dtype, const void* x, void* out, int64_t n, float p, uint64_t seed, void* stream);
+/* out = max(x, 0) by fmaxf: relu(NaN) = 0 (torch returns NaN), relu(-0.0) = +0.0; dx = y > 0 ? dy : 0. */
 hs_status hs_relu_fwd(int32_t dtype, const void* x, void* out, int64_t n, void* stream);
 hs_status hs_relu_bwd(int32_t dtype, const void* dy, const void* y, void* dx, int64_t n, void* stream);
 /* dx = dy * gelu'(u)  (erf GELU). */
@@ -363,13 +371,22 @@ hs_status hs_softmax_fwd(int32_t dtype, const float* S, const int64_t* mask, voi
                          void* stream);
 hs_status hs_softmax_bwd(int32_t dtype, const float* dP, const void* P, void* dS, int64_t rows, int32_t Lk, int32_t ldG,
                          int32_t ldP, float dropout_p, uint64_t seed, void* stream);
-/* BertEmbeddings (token_type_ids == 0): sum_out = word[ids]+pos[l]+type0 ; y = dropout(LN(sum_out)). */
+/* BertEmbeddings (token_type_ids == 0): sum_out = word[ids]+pos[l]+type0 ; y = dropout(LN(sum_out)).
+   Token t of `tokens` sits at position l = t % L; sum_out is rounded to dtype first and the LayerNorm reads the rounded value;
+   the dropout element index of y[t][h] is t * H + h (the mask of hs_dropout over the [tokens][H] tensor).
+   An id outside [0, V) is clamped to 0 or V - 1, not refused (nn.Embedding raises there): intended, it keeps a bad id from
+   reading outside the table, and hs_bert_embed_bwd clamps alike.
+   Preconditions, refused before any launch: no NULL pointer; 4 <= H <= 1024, H % 4 == 0 (HS_ERR_ARG); tokens, L, V >= 1
+   (HS_ERR_UNSUPPORTED). */
 hs_status hs_bert_embed_fwd(int32_t dtype, const int64_t* ids, const float* word, const float* pos, const float* type0,
                             const float* gamma, const float* beta, void* sum_out, void* y, float* mean, float* rstd,
                             int64_t tokens, int32_t L, int32_t H, int32_t V, float eps, float dropout_p, uint64_t seed,
                             void* stream);
 /* dword (zero-filled by the caller) += scatter(dsum by ids), skipping ids == pad_id (nn.Embedding
-   padding_idx; -1 = none); dpos[l] = sum_b dsum[b][l]. */
+   padding_idx; -1 = none); dpos[l] = sum_b dsum[b][l].  dword or dpos may be NULL.  Up to 15360 tokens a table row is the
+   sum of its tokens' rows in token order (the same bits on every run); beyond that float atomics add them in any order.
+   Rows of ids that do not occur keep the caller's zeros.  ids are clamped as in the forward.
+   Preconditions, refused before any launch: ids, dsum not NULL (HS_ERR_ARG); B, L, H, V >= 1 (HS_ERR_UNSUPPORTED). */
 hs_status hs_bert_embed_bwd(int32_t dtype, const int64_t* ids, const void* dsum, float* dword, float* dpos, int32_t B,
                             int32_t L, int32_t H, int32_t V, int32_t pad_id, void* stream);
 /* mean-reduced CrossEntropyLoss(weight, label_smoothing): writes the scalar loss, d loss / d logits

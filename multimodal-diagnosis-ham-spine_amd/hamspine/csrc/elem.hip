@@ -1222,6 +1222,25 @@ static int maxpool_bwd_t(const void* dy, const void* idx, void* dx, int N, int H
     HS_LAUNCH_CHECK();
     return HS_OK;
 }
+// arguments outside what a kernel serves (empty or negative extents): refused with HS_ERR_UNSUPPORTED before any arithmetic or launch
+#define HS_SUPPORTED(cond, ...)                                                              \
+    do {                                                                                     \
+        if (!(cond)) {                                                                       \
+            hs::set_error(__VA_ARGS__);                                                      \
+            return HS_ERR_UNSUPPORTED;                                                       \
+        }                                                                                    \
+    } while (0)
+// shape checks of both max-pool entry points, in front of the divisions by `stride` that give P and Q
+static int maxpool_args(const char* who, int N, int H, int W, int C, int ks, int st, int pad) {
+    HS_REQUIRE(ks <= 15, "%s: window too large (ksize=%d: the arg-max tap is kept in a byte)", who, ks);
+    HS_SUPPORTED(N >= 1 && H >= 1 && W >= 1 && C >= 1, "%s: N=%d H=%d W=%d C=%d must all be >= 1", who, N, H, W, C);
+    HS_SUPPORTED(ks >= 1, "%s: ksize=%d must be >= 1", who, ks);
+    HS_SUPPORTED(st >= 1, "%s: stride=%d must be >= 1", who, st);
+    HS_SUPPORTED(pad >= 0, "%s: pad=%d must be >= 0", who, pad);
+    HS_SUPPORTED((long long)H + 2ll * pad >= ks && (long long)W + 2ll * pad >= ks,
+                 "%s: the %dx%d window is larger than the padded %dx%d input (pad %d)", who, ks, ks, H, W, pad);
+    return HS_OK;
+}
 static void mean_geom(int H, int E, int& tpc, int& gx) {
     const int cg = H / E;
     tpc = 1;
@@ -1461,7 +1480,8 @@ int bert_embed_fwd_rows(int dtype, const int64_t* ids, const float* word, const 
                         const float* beta, void* sum_out, void* y, float* mean, float* rstd, long long tokens, int L, int H, int V,
                         float eps, float dropout_p, unsigned long long seed, const int* nrows, const int* row_of, hipStream_t stream) {
     HS_REQUIRE(ids && word && pos && type0 && gamma && beta && sum_out && y && mean && rstd, "bert_embed: null argument");
-    HS_REQUIRE(H % 4 == 0 && H <= 1024, "bert_embed: H=%d unsupported", H);
+    HS_REQUIRE(H >= 4 && H % 4 == 0 && H <= 1024, "bert_embed: H=%d unsupported", H);
+    HS_SUPPORTED(tokens >= 1 && L >= 1 && V >= 1, "bert_embed: tokens=%lld L=%d V=%d must all be >= 1", tokens, L, V);
     const unsigned th = dropout_p > 0.f ? dropout_thresh(dropout_p) : 0u;
     const float ik = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
     const dim3 g(ceil_div(tokens, 4)), b(256);
@@ -1478,6 +1498,7 @@ int bert_embed_fwd_rows(int dtype, const int64_t* ids, const float* word, const 
 int bert_embed_bwd_rows(int dtype, const int64_t* ids, const void* dsum, float* dword, float* dpos, int B, int L, int H, int V,
                         int pad_id, const int* nrows, const int* row_of, const int* packed_of, hipStream_t s) {
     HS_REQUIRE(ids && dsum, "bert_embed_bwd: null argument");
+    HS_SUPPORTED(B >= 1 && L >= 1 && H >= 1 && V >= 1, "bert_embed_bwd: B=%d L=%d H=%d V=%d must all be >= 1", B, L, H, V);
     const long long tokens = (long long)B * L;
     if (dword) {   // caller zero-fills dword first
         const bool det = tokens <= 15360;                 // match list (4 B per token) + wave totals within 64 KiB of LDS
@@ -1516,13 +1537,14 @@ extern "C" {
 hs_status hs_maxpool_fwd(int32_t dtype, const void* x, void* y, void* idx, int32_t N, int32_t H, int32_t W, int32_t C,
                          int32_t ksize, int32_t stride, int32_t pad, void* stream) {
     HS_REQUIRE(x && y && idx, "maxpool: null argument");
-    HS_REQUIRE(ksize * ksize <= 255, "maxpool: window too large");
+    HS_PROPAGATE(maxpool_args("maxpool", N, H, W, C, ksize, stride, pad));
     const int P = (H + 2 * pad - ksize) / stride + 1, Q = (W + 2 * pad - ksize) / stride + 1;
     return DISPATCH_T(dtype, maxpool_fwd_t, x, y, idx, N, H, W, C, P, Q, ksize, stride, pad, (hipStream_t)stream);
 }
 hs_status hs_maxpool_bwd(int32_t dtype, const void* dy, const void* idx, void* dx, int32_t N, int32_t H, int32_t W,
                          int32_t C, int32_t ksize, int32_t stride, int32_t pad, void* stream) {
     HS_REQUIRE(dy && dx && idx, "maxpool_bwd: null argument");
+    HS_PROPAGATE(maxpool_args("maxpool_bwd", N, H, W, C, ksize, stride, pad));
     const int P = (H + 2 * pad - ksize) / stride + 1, Q = (W + 2 * pad - ksize) / stride + 1;
     return DISPATCH_T(dtype, maxpool_bwd_t, dy, idx, dx, N, H, W, C, P, Q, ksize, stride, pad, (hipStream_t)stream);
 }
