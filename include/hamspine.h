@@ -446,6 +446,55 @@ hs_status hs_sgd_step_multi(int32_t count, float* const* params, const float* co
                             float grad_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------- */
+/* Global gradient-norm clipping without a host sync (csrc/gradclip.hip).  Replaces               */
+/* torch.nn.utils.clip_grad_norm_; no reference counterpart (the reference trains without it).    */
+/* The norm and its clip coefficient stay on the device in a four-float record                    */
+/*   rec[0] = the global 2-norm, rounded once to f32                                              */
+/*   rec[1] = the coefficient fminf(max_norm / (rec[0] + 1e-6f), 1.0f) in f32, a NaN kept          */
+/*   rec[2] = 1 if rec[0] is finite, else 0                                                       */
+/*   rec[3] = 1 if the step is to be skipped (skip_nonfinite set and rec[2] == 0), else 0          */
+/* that the step kernels below read.  Nothing here reads the device back.                         */
+/* ------------------------------------------------------------------------------------------- */
+#define HS_GRADCLIP_MAX 128
+/* Sums of squares of `count` <= HS_GRADCLIP_MAX f32 tensors (n[i] >= 0 elements; grads[i] 4-byte aligned, any n[i] including
+   0), in f64.  Every workgroup writes the sum over its fixed share of one tensor into its own slot: the call fills
+   hs_grad_norm_partials(count, n) slots of `partials`, in tensor order, and further calls are laid end to end behind them.
+   No atomics; the slot and the order of every sum depend on (count, n) alone, so a rerun repeats bitwise.
+   Replaces the norm pass of torch.nn.utils.clip_grad_norm_; no reference counterpart.
+   Refused before any launch (HS_ERR_ARG): count outside [0, HS_GRADCLIP_MAX], a NULL table, a NULL or misaligned entry,
+   n[i] < 0, partials NULL. */
+hs_status hs_grad_sumsq_multi(int32_t count, const float* const* grads, const int64_t* n, double* partials, void* stream);
+/* slots the call above writes; -1 for arguments it refuses.  No reference counterpart. */
+int64_t hs_grad_norm_partials(int32_t count, const int64_t* n);
+/* One workgroup adds `n_partials` slots in a fixed order in f64 and writes rec[0..3] as stated above.  With
+   skip_nonfinite == 0 a non-finite norm follows the arithmetic as torch does: a NaN norm gives a NaN coefficient, an infinite
+   one the coefficient 0.  max_norm = +inf: coefficient 1 (monitor only).
+   Replaces the norm reduction and clip_coef arithmetic of torch.nn.utils.clip_grad_norm_; no reference counterpart.
+   Refused before any launch: partials or rec NULL, max_norm negative or NaN (HS_ERR_ARG); n_partials < 1
+   (HS_ERR_UNSUPPORTED). */
+hs_status hs_grad_norm_finish(const double* partials, int64_t n_partials, float max_norm, int32_t skip_nonfinite, float* rec,
+                              void* stream);
+/* g *= rec[1] in place over `count` <= HS_GRADCLIP_MAX tensors; every thread leaves at once (no write traffic) when
+   rec[1] == 1.0f or rec[3] is set.  The stand-alone route for optimizers without a fused one.
+   Replaces the scaling pass of torch.nn.utils.clip_grad_norm_; no reference counterpart.  Refusals as hs_grad_sumsq_multi,
+   and rec NULL. */
+hs_status hs_grad_scale_multi(int32_t count, float* const* grads, const int64_t* n, const float* rec, void* stream);
+/* hs_adam_step_multi_shadow with the gradient multiplied by grad_scale, then by rec[1]; with rec[3] set the launch leaves
+   p, exp_avg, exp_avg_sq and the bf16 shadow untouched.  With rec[1] == 1 the results are bitwise those of
+   hs_adam_step_multi_shadow.  Replaces torch.nn.utils.clip_grad_norm_ in front of torch.optim.Adam/AdamW.step; no reference
+   counterpart.  Refused (HS_ERR_ARG): count < 0, step < 1, rec NULL, a NULL table other than bf16_shadow. */
+hs_status hs_adam_step_multi_clip(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
+                                  float* const* exp_avg_sq, void* const* bf16_shadow, const int64_t* n, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, int32_t step, int32_t decoupled, float grad_scale,
+                                  const float* rec, void* stream);
+/* hs_sgd_step_multi likewise: the gradient times grad_scale, then rec[1]; with rec[3] set p and the momentum buffer stay as
+   they are.  Replaces torch.nn.utils.clip_grad_norm_ in front of torch.optim.SGD.step; no reference counterpart.
+   Refused (HS_ERR_ARG): count < 0, momentum without buffers, rec NULL, a NULL table. */
+hs_status hs_sgd_step_multi_clip(int32_t count, float* const* params, const float* const* grads, float* const* momentum_buf,
+                                 const int64_t* n, float lr, float momentum, float weight_decay, int32_t nesterov, int32_t first,
+                                 float grad_scale, const float* rec, void* stream);
+
+/* ------------------------------------------------------------------------------------------- */
 /* Muon (csrc/muon.hip): the Muon group of MuonWithAuxAdam, reference scripts/train.py:262-307     */
 /* (`from muon import MuonWithAuxAdam`).  A parameter is the matrix (rows = shape[0], cols = numel  */
 /* / rows) its dense f32 memory holds.  The matrices of one (rows, cols) group are packed into one  */

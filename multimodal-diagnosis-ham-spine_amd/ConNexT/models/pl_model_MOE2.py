@@ -10,7 +10,8 @@ What differs from the reference:
     `val_auroc` and `validation_per_class_metrics` all name that meter; like the reference's metric objects it adds no
     state-dict keys.  A class without positives has AUROC NaN and is left out of `val_AUROC` (torchmetrics: 0 with a warning).
   * the loss is `hamspine.functional.cross_entropy`, the optimizer `hamspine.optim.FusedAdam` (Adam with L2 weight decay, as
-    torch.optim.Adam).
+    torch.optim.Adam).  With `gradient_clip_val` in config['train'] it clips the global gradient norm inside its step
+    (`FusedAdam(max_grad_norm=...)`: .grad stays unscaled; pass no `gradient_clip_val` to the Trainer as well).
 """
 import torch
 import torch.nn as nn
@@ -186,7 +187,10 @@ class Model4AAAI_MoE(_Base):
         self._meter.reset()
 
     def configure_optimizers(self):
-        optimizer = FusedAdam(self.parameters(), lr=self.hparams.learning_rate, weight_decay=1e-5)
+        # config['train']['gradient_clip_val'] (the stock Trainer argument, given here in the config): global gradient-norm
+        # clipping inside the fused step, no host sync; absent: the optimizer as it was
+        optimizer = FusedAdam(self.parameters(), lr=self.hparams.learning_rate, weight_decay=1e-5,
+                              max_grad_norm=self.hparams.config['train'].get('gradient_clip_val'))
         scheduler = {
             "scheduler": torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=10, eta_min=1e-6),
             "interval": "epoch",

@@ -189,6 +189,7 @@ B_KC, B_RC, B_WDGRAD, B_CONV = _const("B_KC", "B_RC", "B_WDGRAD", "B_CONV")
 ACT_NONE, ACT_RELU, ACT_GELU = _const("ACT_NONE", "ACT_RELU", "ACT_GELU")
 MUL_NONE, MUL_GELU_GRAD, MUL_RELU_MASK = _const("MUL_NONE", "MUL_GELU_GRAD", "MUL_RELU_MASK")
 CAST_MAX, ADAM_MAX, MUON_MAX, MUON_PARTIALS = _const("CAST_MAX", "ADAM_MAX", "MUON_MAX", "MUON_PARTIALS")
+GRADCLIP_MAX, = _const("GRADCLIP_MAX")
 RESNET_MAX_BLOCKS, RESNET_MAX_TAPS, BERT_MAX_LAYERS = _const("RESNET_MAX_BLOCKS", "RESNET_MAX_TAPS", "BERT_MAX_LAYERS")
 
 # ------------------------------------------------------------------------------------------ the library

@@ -1132,9 +1132,21 @@ struct AdamTable {
     long long n[HS_ADAM_MAX];
     bf16_t* h[HS_ADAM_MAX];      // optional bf16 shadow of p (the compute-dtype copy the towers read), written with the update
 };
+// CLIP (hs_adam_step_multi_clip): the gradient is also multiplied by rec[1], and rec[3] != 0 skips the step (the record of
+// hs_grad_norm_finish, csrc/gradclip.hip).  The record is a trailing parameter pack: one `const float*` with CLIP, empty without, so
+// the CLIP = false kernel is the kernel as it was, argument list included.
+__device__ __forceinline__ const float* clip_rec(const float* rec) { return rec; }
+template <bool CLIP, typename... Rec>
 __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamTable t, float lr, float beta1, float beta2, float eps,
                                                          float wd, float bc1, float bc2_sqrt, int decoupled,
-                                                         float grad_scale) {
+                                                         float grad_scale, Rec... rec) {
+    static_assert(sizeof...(Rec) == (CLIP ? 1 : 0), "the record comes with CLIP and only with it");
+    float clip = 1.f;
+    if constexpr (CLIP) {
+        const float* r = clip_rec(rec...);
+        if (r[3] != 0.f) return;
+        clip = r[1];
+    }
     const int e = blockIdx.y;
     float* p = t.p[e];
     const float* g = t.g[e];
@@ -1143,6 +1155,7 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamTable t, floa
     const long long n = t.n[e];
     auto upd = [&](float& pi, float gi, float& mi, float& vi) {
         gi *= grad_scale;
+        if constexpr (CLIP) gi *= clip;
         if (decoupled) pi *= 1.f - lr * wd;
         else gi += wd * pi;
         mi = beta1 * mi + (1.f - beta1) * gi;
@@ -1177,8 +1190,17 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamTable t, floa
 
 // fused multi-tensor SGD (torch.optim.SGD semantics: weight decay added to the gradient, optional momentum buffer with
 // dampening 0, optional Nesterov); `first` = the momentum buffers are uninitialised (torch seeds them with the gradient)
+// CLIP, Rec (hs_sgd_step_multi_clip): as in adam_multi_kernel
+template <bool CLIP, typename... Rec>
 __global__ __launch_bounds__(256) void sgd_multi_kernel(const AdamTable t, float lr, float momentum, float wd, int nesterov,
-                                                        int first, float grad_scale) {
+                                                        int first, float grad_scale, Rec... rec) {
+    static_assert(sizeof...(Rec) == (CLIP ? 1 : 0), "the record comes with CLIP and only with it");
+    float clip = 1.f;
+    if constexpr (CLIP) {
+        const float* r = clip_rec(rec...);
+        if (r[3] != 0.f) return;
+        clip = r[1];
+    }
     const int e = blockIdx.y;
     float* p = t.p[e];
     const float* g = t.g[e];
@@ -1186,6 +1208,7 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(const AdamTable t, float
     const long long n = t.n[e];
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         float gi = g[i] * grad_scale;
+        if constexpr (CLIP) gi *= clip;
         const float pi = p[i];
         if (wd != 0.f) gi += wd * pi;
         if (buf) {
@@ -1742,9 +1765,10 @@ hs_status hs_cross_entropy(const float* logits, const int64_t* labels, const flo
     HS_LAUNCH_CHECK();
     return HS_OK;
 }
-hs_status hs_sgd_step_multi(int32_t count, float* const* params, const float* const* grads, float* const* momentum_buf,
-                            const int64_t* n, float lr, float momentum, float weight_decay, int32_t nesterov, int32_t first,
-                            float grad_scale, void* stream) {
+// rec NULL: the plain step; else the clipped one (csrc/gradclip.hip)
+static int sgd_step(int32_t count, float* const* params, const float* const* grads, float* const* momentum_buf, const int64_t* n,
+                    float lr, float momentum, float weight_decay, int32_t nesterov, int32_t first, float grad_scale,
+                    const float* rec, void* stream) {
     HS_REQUIRE(count >= 0 && (momentum == 0.f || momentum_buf), "sgd: bad argument");
     for (int base = 0; base < count; base += HS_ADAM_MAX) {
         AdamTable t;
@@ -1759,11 +1783,27 @@ hs_status hs_sgd_step_multi(int32_t count, float* const* params, const float* co
             mx = std::max<long long>(mx, t.n[i]);
         }
         const int gx = (int)std::min<long long>(std::max<long long>((mx + 1023) / 1024, 1), 512);
-        hipLaunchKernelGGL(sgd_multi_kernel, dim3(gx, cnt), dim3(256), 0, (hipStream_t)stream, t, lr, momentum, weight_decay,
-                           nesterov, first, grad_scale);
+        if (rec)
+            hipLaunchKernelGGL((sgd_multi_kernel<true, const float*>), dim3(gx, cnt), dim3(256), 0, (hipStream_t)stream, t, lr, momentum,
+                               weight_decay, nesterov, first, grad_scale, rec);
+        else
+            hipLaunchKernelGGL(sgd_multi_kernel<false>, dim3(gx, cnt), dim3(256), 0, (hipStream_t)stream, t, lr, momentum,
+                               weight_decay, nesterov, first, grad_scale);
         HS_LAUNCH_CHECK();
     }
     return HS_OK;
+}
+hs_status hs_sgd_step_multi(int32_t count, float* const* params, const float* const* grads, float* const* momentum_buf,
+                            const int64_t* n, float lr, float momentum, float weight_decay, int32_t nesterov, int32_t first,
+                            float grad_scale, void* stream) {
+    return sgd_step(count, params, grads, momentum_buf, n, lr, momentum, weight_decay, nesterov, first, grad_scale, nullptr, stream);
+}
+hs_status hs_sgd_step_multi_clip(int32_t count, float* const* params, const float* const* grads, float* const* momentum_buf,
+                                 const int64_t* n, float lr, float momentum, float weight_decay, int32_t nesterov, int32_t first,
+                                 float grad_scale, const float* rec, void* stream) {
+    HS_REQUIRE(rec, "sgd_clip: rec is NULL");
+    HS_REQUIRE(count <= 0 || (params && grads && n), "sgd_clip: NULL table");
+    return sgd_step(count, params, grads, momentum_buf, n, lr, momentum, weight_decay, nesterov, first, grad_scale, rec, stream);
 }
 hs_status hs_adam_step_multi(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
                              float* const* exp_avg_sq, const int64_t* n, float lr, float beta1, float beta2, float eps,
@@ -1771,10 +1811,11 @@ hs_status hs_adam_step_multi(int32_t count, float* const* params, const float* c
     return hs_adam_step_multi_shadow(count, params, grads, exp_avg, exp_avg_sq, nullptr, n, lr, beta1, beta2, eps, weight_decay, step,
                                      decoupled, grad_scale, stream);
 }
-hs_status hs_adam_step_multi_shadow(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
-                                    float* const* exp_avg_sq, void* const* bf16_shadow, const int64_t* n, float lr, float beta1,
-                                    float beta2, float eps, float weight_decay, int32_t step, int32_t decoupled,
-                                    float grad_scale, void* stream) {
+// rec NULL: the plain step; else the clipped one (csrc/gradclip.hip)
+static int adam_step(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
+                     float* const* exp_avg_sq, void* const* bf16_shadow, const int64_t* n, float lr, float beta1, float beta2,
+                     float eps, float weight_decay, int32_t step, int32_t decoupled, float grad_scale, const float* rec,
+                     void* stream) {
     HS_REQUIRE(count >= 0 && step >= 1, "adam: bad argument");
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
@@ -1793,10 +1834,30 @@ hs_status hs_adam_step_multi_shadow(int32_t count, float* const* params, const f
             mx = std::max<long long>(mx, t.n[i]);
         }
         const int gx = (int)std::min<long long>(std::max<long long>((mx + 4095) / 4096, 1), 256);
-        hipLaunchKernelGGL(adam_multi_kernel, dim3(gx, cnt), dim3(256), 0, (hipStream_t)stream, t, lr, beta1, beta2, eps,
-                           weight_decay, bc1, bc2s, decoupled, grad_scale);
+        if (rec)
+            hipLaunchKernelGGL((adam_multi_kernel<true, const float*>), dim3(gx, cnt), dim3(256), 0, (hipStream_t)stream, t, lr, beta1, beta2, eps,
+                               weight_decay, bc1, bc2s, decoupled, grad_scale, rec);
+        else
+            hipLaunchKernelGGL(adam_multi_kernel<false>, dim3(gx, cnt), dim3(256), 0, (hipStream_t)stream, t, lr, beta1, beta2, eps,
+                               weight_decay, bc1, bc2s, decoupled, grad_scale);
         HS_LAUNCH_CHECK();
     }
     return HS_OK;
+}
+hs_status hs_adam_step_multi_shadow(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
+                                    float* const* exp_avg_sq, void* const* bf16_shadow, const int64_t* n, float lr, float beta1,
+                                    float beta2, float eps, float weight_decay, int32_t step, int32_t decoupled,
+                                    float grad_scale, void* stream) {
+    return adam_step(count, params, grads, exp_avg, exp_avg_sq, bf16_shadow, n, lr, beta1, beta2, eps, weight_decay, step, decoupled,
+                     grad_scale, nullptr, stream);
+}
+hs_status hs_adam_step_multi_clip(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
+                                  float* const* exp_avg_sq, void* const* bf16_shadow, const int64_t* n, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, int32_t step, int32_t decoupled, float grad_scale,
+                                  const float* rec, void* stream) {
+    HS_REQUIRE(rec, "adam_clip: rec is NULL");
+    HS_REQUIRE(count <= 0 || (params && grads && exp_avg && exp_avg_sq && n), "adam_clip: NULL table");
+    return adam_step(count, params, grads, exp_avg, exp_avg_sq, bf16_shadow, n, lr, beta1, beta2, eps, weight_decay, step, decoupled,
+                     grad_scale, rec, stream);
 }
 }

@@ -6,6 +6,10 @@ state_dict layout (step / exp_avg / exp_avg_sq).  One launch per 32 tensors inst
 
 MuonWithAuxAdam (scripts/train.py:262-307, `from muon import MuonWithAuxAdam`): Muon groups on csrc/muon.hip and batched hs_gemm
 Newton-Schulz iterations, auxiliary groups on the same Adam kernel.
+
+Global gradient-norm clipping (csrc/gradclip.hip; replaces torch.nn.utils.clip_grad_norm_, no reference counterpart):
+`max_grad_norm=` on FusedAdam / FusedAdamW / FusedSGD clips inside the step without a host sync and leaves .grad unscaled;
+`clip_grad_norm_` is the in-place stand-alone form for every other optimizer.
 """
 import ctypes as C
 
@@ -26,20 +30,220 @@ def _knock_adam():
 _KNOCK_ADAM = None
 
 
-class _FusedAdamBase(torch.optim.Optimizer):
+# ------------------------------------------------------------------------------------------------------------------------
+# global gradient-norm clipping on csrc/gradclip.hip (replaces torch.nn.utils.clip_grad_norm_; no reference counterpart)
+# ------------------------------------------------------------------------------------------------------------------------
+def _dense(t):
+    """every element of t's memory span belongs to exactly one index (what a flat pass over numel() elements needs)"""
+    if t.is_contiguous():
+        return True
+    expect = 1
+    for size, stride in sorted(((s, st) for s, st in zip(t.shape, t.stride()) if s != 1), key=lambda d: d[1]):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+def _clip_settings(max_grad_norm, nonfinite):
+    """validated (max_grad_norm as a float or None, skip flag)"""
+    if nonfinite not in ("propagate", "skip"):
+        raise ValueError(f'nonfinite must be "propagate" or "skip", not {nonfinite!r}')
+    if max_grad_norm is None:
+        return None, nonfinite == "skip"
+    max_grad_norm = float(max_grad_norm)
+    if not max_grad_norm >= 0.0:
+        raise ValueError(f"max_grad_norm must be >= 0 (float('inf') monitors only), not {max_grad_norm}")
+    return max_grad_norm, nonfinite == "skip"
+
+
+class _GradNorm:
+    """The sum-of-squares and finish launches over one set of gradients, and the device record they leave:
+    rec = [norm, clip coefficient, finite, skip] (include/hamspine.h).  Nothing is read back.
+
+    Host cost (the note of _FusedAdamBase._update applies: a C2 step has ~400 gradient tensors): the pointer and size tables,
+    the slot offsets of the launches and the buffers are built once per parameter set and revalidated against the gradient
+    pointers of the step; the partials and the record are allocated once per device."""
+
+    def __init__(self):
+        self._tables = {}
+        self._bufs = {}         # device -> {"rec": f32 [4], "partials": f64 [slots]}
+
+    def _buffers(self, dev, slots, fresh_rec=False):
+        b = self._bufs.get(dev)
+        if b is None:
+            b = self._bufs[dev] = {"rec": torch.empty(4, dtype=torch.float32, device=dev), "partials": None}
+        if b["partials"] is None or b["partials"].numel() < slots:
+            b["partials"] = torch.empty(max(slots, 1), dtype=torch.float64, device=dev)
+        rec = torch.empty(4, dtype=torch.float32, device=dev) if fresh_rec else b["rec"]
+        return rec, b["partials"]
+
+    def rec(self, dev=None):
+        """the record of the last measure() (on `dev`, or on the only device used so far), or None"""
+        if dev is None:
+            dev = next(iter(self._bufs), None)
+        b = self._bufs.get(dev)
+        return None if b is None else b["rec"]
+
+    def measure(self, ps, max_norm, skip, fresh_rec=False):
+        """ps: parameters with a gradient.  Enqueues the launches on the current stream -> (rec tensor, table entry)"""
+        lib = L.lib()
+        key = (len(ps), id(ps[0]), id(ps[-1]))
+        ent = self._tables.get(key)
+        ids = [id(p) for p in ps]
+        if ent is None or ent["ids"] != ids:
+            rt.need_gpu(*ps)
+            dev = ps[0].device
+            if any(p.device != dev for p in ps):
+                raise L.HamspineError("gradient-norm clipping expects all parameters on one device")
+            if len(self._tables) >= 8:          # parameter sets come and go (unused parameters): keep the cache small
+                self._tables.clear()
+            ent = self._tables[key] = {"ids": ids, "dev": dev, "gptrs": None, "chunks": None, "slots": 0}
+        if any(p.grad.dtype != torch.float32 for p in ps):       # (every call: a pointer and a size say nothing about the type)
+            raise L.HamspineError("gradient-norm clipping expects f32 gradients")
+        gptrs = [(p.grad.data_ptr(), p.grad.numel()) for p in ps]
+        if gptrs != ent["gptrs"]:
+            rt.need_gpu(*[p.grad for p in ps])
+            for p in ps:
+                g = p.grad
+                if not _dense(g):          # rare: an expanded or strided gradient produced outside our nodes
+                    g2 = torch.empty_like(p, memory_format=torch.preserve_format)
+                    g2.copy_(g)
+                    p.grad = g2
+            gptrs = [(p.grad.data_ptr(), p.grad.numel()) for p in ps]
+            chunks, off = [], 0
+            for base in range(0, len(ps), L.GRADCLIP_MAX):
+                sel = ps[base:base + L.GRADCLIP_MAX]
+                n = len(sel)
+                cnt = (C.c_int64 * n)(*[gn for _, gn in gptrs[base:base + n]])
+                slots = int(lib.hs_grad_norm_partials(n, cnt))
+                if slots < 0:
+                    raise L.HamspineError("hs_grad_norm_partials refused the sizes")
+                chunks.append({"n": n, "garr": (C.c_void_p * n)(*[gp for gp, _ in gptrs[base:base + n]]), "cnt": cnt, "off": off})
+                off += slots
+            ent["gptrs"], ent["chunks"], ent["slots"] = gptrs, chunks, off
+        rec, partials = self._buffers(ent["dev"], ent["slots"], fresh_rec)
+        s, base = rt.stream(), partials.data_ptr()
+        for ch in ent["chunks"]:
+            L.check(lib.hs_grad_sumsq_multi(ch["n"], ch["garr"], ch["cnt"], base + 8 * ch["off"], s), "hs_grad_sumsq_multi")
+        L.check(lib.hs_grad_norm_finish(base, ent["slots"], max_norm, 1 if skip else 0, rec.data_ptr(), s), "hs_grad_norm_finish")
+        return rec, ent
+
+    def scale(self, ent, rec):
+        lib, s = L.lib(), rt.stream()
+        for ch in ent["chunks"]:
+            L.check(lib.hs_grad_scale_multi(ch["n"], ch["garr"], ch["cnt"], rec.data_ptr(), s), "hs_grad_scale_multi")
+
+
+_standalone = _GradNorm()
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False):
+    """torch.nn.utils.clip_grad_norm_ on the HIP kernels of csrc/gradclip.hip: one read of every gradient for the norm (f64
+    sums in a fixed order), one finish launch, one in-place scaling pass that writes nothing when the coefficient is 1.
+    Returns the pre-clip global norm as a 0-dim f32 device tensor (a CPU zero when no parameter has a gradient, as torch does);
+    nothing is read back, except that error_if_nonfinite=True
+    reads the `finite` flag and raises RuntimeError before scaling, as torch does.  norm_type other than 2 raises
+    NotImplementedError.  The route for optimizers without a fused one (MuonWithAuxAdam); FusedAdam / FusedAdamW / FusedSGD
+    take max_grad_norm= instead and never scale .grad."""
+    if float(norm_type) != 2.0:
+        raise NotImplementedError(f"hamspine.optim.clip_grad_norm_: only norm_type=2 is implemented, not {norm_type}")
+    max_norm, _ = _clip_settings(float(max_norm), "propagate")          # (None: TypeError, as in torch)
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    ps = [p for p in parameters if p.grad is not None]
+    if not ps:
+        return torch.zeros(())
+    rec, ent = _standalone.measure(ps, max_norm, False, fresh_rec=True)
+    if error_if_nonfinite and float(rec[2].item()) == 0.0:
+        raise RuntimeError("The total norm of order 2.0 for gradients from `parameters` is non-finite, so it cannot be "
+                           "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                           "`error_if_nonfinite=False`")
+    _standalone.scale(ent, rec)
+    return rec[0]
+
+
+class _ClipMixin:
+    """max_grad_norm / nonfinite of the fused optimizers.  The settings are attributes: param_groups and state_dict() keep
+    torch.optim's layout."""
+
+    def _clip_init(self, max_grad_norm, nonfinite):
+        self.max_grad_norm, self._skip_nonfinite = _clip_settings(max_grad_norm, nonfinite)
+        self.nonfinite = nonfinite
+        self._gradnorm = _GradNorm() if self.max_grad_norm is not None else None
+
+    # torch.optim.Optimizer pickles defaults, state and param_groups only: carry the two settings, rebuild the launch cache
+    def __getstate__(self):
+        st = dict(super().__getstate__())
+        st["max_grad_norm"], st["nonfinite"] = getattr(self, "max_grad_norm", None), getattr(self, "nonfinite", "propagate")
+        return st
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._clip_init(self.__dict__.get("max_grad_norm"), self.__dict__.get("nonfinite", "propagate"))
+
+    def _clip_measure(self, grad_scale):
+        """enqueues the norm launches over the gradients of ALL groups -> the device record, or None without any gradient"""
+        if grad_scale != 1.0:
+            raise L.HamspineError("max_grad_norm together with step(grad_scale != 1) is not supported: the norm is taken of "
+                                  ".grad as it stands")
+        ps = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
+        if not ps:
+            return None
+        return self._gradnorm.measure(ps, self.max_grad_norm, self._skip_nonfinite)[0]
+
+    def _rec_view(self, i):
+        rec = None if getattr(self, "_gradnorm", None) is None else self._gradnorm.rec()
+        return None if rec is None else rec[i]
+
+    @property
+    def grad_norm(self):
+        """0-dim f32 device view: the global gradient norm before clipping of the last step (None before the first, or without
+        max_grad_norm).  Rewritten by the next step: clone it to keep it."""
+        return self._rec_view(0)
+
+    @property
+    def grad_clip_coef(self):
+        """0-dim device view of the coefficient the last step multiplied the gradients by (see grad_norm)"""
+        return self._rec_view(1)
+
+    @property
+    def grad_finite(self):
+        """0-dim device view: 1.0 if the last step's norm was finite, else 0.0 (see grad_norm)"""
+        return self._rec_view(2)
+
+
+class _FusedAdamBase(_ClipMixin, torch.optim.Optimizer):
     _decoupled = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, overlap_backward=None,
-                 overlap_chunk=8 << 20):
+                 overlap_chunk=8 << 20, max_grad_norm=None, nonfinite="propagate"):
         """overlap_backward: update parameters while backward is still running -- as soon as `overlap_chunk` elements
         worth of gradients are final (post-accumulate hooks) their fused update is enqueued on a side stream ordered
         behind the streams that produced them; step() flushes the rest and joins.  Same arithmetic as stepping after
         backward; valid whenever nothing between backward and step() reads all gradients at once (no global-norm
         clipping, no gradient accumulation over several backwards), which is how the reference trains
-        (scripts/train.py:373-385, mibf_net/train_resnet.py:29-33)."""
+        (scripts/train.py:373-385, mibf_net/train_resnet.py:29-33).
+
+        max_grad_norm: clip the global 2-norm of the gradients of ALL param groups to this value, as
+        torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm) in front of step() would, without a host sync and
+        without the scaling pass: step() reads every gradient once for the norm (csrc/gradclip.hip), the coefficient
+        min(max_grad_norm / (norm + 1e-6), 1) stays on the device and the step kernel multiplies by it.  Departure from the torch
+        route: .grad is left UNSCALED.  float("inf") monitors only.  After a step `grad_norm`, `grad_clip_coef` and `grad_finite`
+        are 0-dim device views of the result (no .item() needed to log them; the next step rewrites them).  None (default): step()
+        is the code path it was.  Refused together with overlap_backward=True (the norm needs every gradient) and with
+        step(grad_scale != 1).
+        nonfinite: "propagate" (default) lets an inf / NaN norm follow torch's arithmetic (coefficient 0 / NaN); "skip" leaves
+        parameters, moments and bf16 shadows untouched for that step.  A skipped step still advances state["step"]: the counter
+        is a host integer and the host never learns that the step was skipped."""
+        self._clip_init(max_grad_norm, nonfinite)
+        if overlap_backward and self.max_grad_norm is not None:
+            raise ValueError("max_grad_norm needs all gradients before the first update: it cannot be combined with "
+                             "overlap_backward=True")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if overlap_backward is None:       # (HAMSPINE_ADAM_OVERLAP=1: A/B measurements of the mode without touching the caller)
-            overlap_backward = _os.environ.get("HAMSPINE_ADAM_OVERLAP", "0") == "1"
+            overlap_backward = _os.environ.get("HAMSPINE_ADAM_OVERLAP", "0") == "1" and self.max_grad_norm is None
         self._overlap = bool(overlap_backward)
         self._chunk = int(_os.environ.get("HAMSPINE_ADAM_CHUNK", "0")) << 20 or int(overlap_chunk)
         self._pending, self._pending_n = [], 0
@@ -111,20 +315,23 @@ class _FusedAdamBase(torch.optim.Optimizer):
             if self._stream is not None:
                 torch.cuda.current_stream(self._stream.device).wait_stream(self._stream)
             return loss
+        rec = self._clip_measure(grad_scale) if getattr(self, "max_grad_norm", None) is not None else None
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if ps:
-                self._update(group, ps, grad_scale)
+                self._update(group, ps, grad_scale, rec)
         return loss
 
-    def _update(self, group, ps, grad_scale):
+    def _update(self, group, ps, grad_scale, rec=None):
         """one fused launch (per 32 tensors) for the parameters `ps` of `group`, on the current stream.
 
         Host cost matters here (a C2 step has ~400 parameter tensors; the first version spent 1.5 ms per step in this
         function): everything that does not move between steps -- parameter / moment pointer tables, sizes, strides, the
         per-tensor checks -- is built once per parameter set, the step counter is ONE shared 0-dim tensor per chunk
         (state[p]["step"] of every tensor in it), and the gradient pointer table is rebuilt only when a gradient pointer
-        changed (the tower executors and hamspine.ddp hand out the same gradient memory every step)."""
+        changed (the tower executors and hamspine.ddp hand out the same gradient memory every step).
+
+        rec: the device record of the step's gradient norm (_GradNorm): the launch is hs_adam_step_multi_clip."""
         global _KNOCK_ADAM
         if _KNOCK_ADAM is None:
             _KNOCK_ADAM = _knock_adam()
@@ -164,7 +371,7 @@ class _FusedAdamBase(torch.optim.Optimizer):
             sel, n = ch["sel"], ch["n"]
             if [p.data_ptr() for p in sel] != ch["ptrs"]:     # a parameter was re-allocated (.to(), load)
                 cache.pop(key, None)
-                return self._update(group, ps, grad_scale)
+                return self._update(group, ps, grad_scale, rec)
             gptrs = [p.grad.data_ptr() for p in sel]
             if gptrs != ch["gptrs"]:
                 for p, st in zip(sel, ch["strides"]):
@@ -185,7 +392,7 @@ class _FusedAdamBase(torch.optim.Optimizer):
             st_all = self.state
             if any(st_all[p]["step"] is not ch["step"] for p in sel):
                 cache.pop(key, None)
-                return self._update(group, ps, grad_scale)
+                return self._update(group, ps, grad_scale, rec)
             ch["step_host"] += 1
             ch["step"].fill_(ch["step_host"])                  # 0-dim CPU tensor: no device work
             # bf16 shadows the towers registered for these parameters (hamspine.rt): written by the same kernel, so the next
@@ -194,6 +401,12 @@ class _FusedAdamBase(torch.optim.Optimizer):
                 hp = [rt.shadow_ptr_of(p) for p in sel]
                 ch["h"] = (C.c_void_p * n)(*hp) if any(hp) else None
                 ch["shadow_epoch"] = rt.shadow_epoch()
+            if rec is not None:
+                L.check(lib.hs_adam_step_multi_clip(
+                    n, ch["p"], ch["garr"], ch["m"], ch["v"], ch["h"], ch["cnt"], float(group["lr"]), b1, b2, group["eps"],
+                    group["weight_decay"], ch["step_host"], 1 if self._decoupled else 0, float(grad_scale), rec.data_ptr(),
+                    rt.stream()), "hs_adam_step_multi_clip")
+                continue
             L.check(lib.hs_adam_step_multi_shadow(
                 n, ch["p"], ch["garr"], ch["m"], ch["v"], ch["h"], ch["cnt"], float(group["lr"]), b1, b2, group["eps"],
                 group["weight_decay"], ch["step_host"], 1 if self._decoupled else 0, float(grad_scale), rt.stream()),
@@ -225,7 +438,8 @@ class MuonWithAuxAdam(_FusedAdamBase):
 
     state_dict layout: momentum_buffer / step, exp_avg, exp_avg_sq.  Parameters without a gradient are skipped (the published
     package substitutes zeros to keep data-parallel ranks in lock-step; under hamspine.ddp every rank sees every gradient).
-    f32 parameters and gradients only; there is no overlap_backward."""
+    f32 parameters and gradients only; there is no overlap_backward and no max_grad_norm: clip with
+    hamspine.optim.clip_grad_norm_(parameters, max_norm) in front of step()."""
     _decoupled = True
 
     def __init__(self, param_groups):
@@ -244,6 +458,7 @@ class MuonWithAuxAdam(_FusedAdamBase):
                 for k, v in (("lr", 3e-4), ("betas", (0.9, 0.95)), ("eps", 1e-10), ("weight_decay", 0.0)):
                     g.setdefault(k, v)
             groups.append(g)
+        self._clip_init(None, "propagate")      # no fused clipping here: hamspine.optim.clip_grad_norm_ in front of step()
         torch.optim.Optimizer.__init__(self, groups, dict())
         self._plans = {}
 
@@ -357,13 +572,18 @@ class MuonWithAuxAdam(_FusedAdamBase):
                                         float(group["lr"]), float(group["weight_decay"]), s), "hs_muon_apply_multi")
 
 
-class FusedSGD(torch.optim.Optimizer):
+class FusedSGD(_ClipMixin, torch.optim.Optimizer):
     """torch.optim.SGD (weight decay, momentum with dampening 0, Nesterov) on hs_sgd_step_multi: the reference's fallback
-    optimizer (scripts/train.py:309).  Same hyper-parameters, param_groups and state_dict layout (momentum_buffer)."""
+    optimizer (scripts/train.py:309).  Same hyper-parameters, param_groups and state_dict layout (momentum_buffer).
 
-    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False):
+    max_grad_norm / nonfinite: global gradient-norm clipping inside the step, as FusedAdam documents it (hs_sgd_step_multi_clip;
+    .grad stays unscaled; with nonfinite="skip" a skipped step leaves parameters and momentum buffers untouched.  A buffer whose
+    seeding step was skipped holds zeros, and the next step's momentum * 0 + g seeds it exactly as torch would have)."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, max_grad_norm=None, nonfinite="propagate"):
         if nesterov and momentum <= 0:
             raise ValueError("Nesterov momentum requires a momentum")
+        self._clip_init(max_grad_norm, nonfinite)
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov))
 
     @torch.no_grad()
@@ -373,6 +593,7 @@ class FusedSGD(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = L.lib()
+        rec = self._clip_measure(grad_scale) if getattr(self, "max_grad_norm", None) is not None else None
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -394,12 +615,22 @@ class FusedSGD(torch.optim.Optimizer):
                         g2.copy_(p.grad)
                         p.grad = g2
                     if mom != 0 and first:
-                        self.state[p]["momentum_buffer"] = torch.empty_like(p, memory_format=torch.preserve_format)
+                        # the kernel seeds the buffer with the gradient (first = 1).  A clipped launch may be skipped on the
+                        # device and then stores nothing: the buffer starts as zeros, so that the next step (first = 0:
+                        # momentum * 0 + g) seeds it with the same bits
+                        new = torch.zeros_like if rec is not None else torch.empty_like
+                        self.state[p]["momentum_buffer"] = new(p, memory_format=torch.preserve_format)
                 arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
                 bufs = arr([self.state[p]["momentum_buffer"] for p in sel]) if mom != 0 else None
                 cnt = (C.c_int64 * n)(*[p.numel() for p in sel])
-                L.check(lib.hs_sgd_step_multi(n, arr(sel), arr([p.grad for p in sel]), bufs, cnt, float(group["lr"]), mom,
-                                              float(group["weight_decay"]), 1 if group["nesterov"] else 0, 1 if first else 0,
-                                              float(grad_scale), rt.stream()), "hs_sgd_step_multi")
+                if rec is not None:
+                    L.check(lib.hs_sgd_step_multi_clip(n, arr(sel), arr([p.grad for p in sel]), bufs, cnt, float(group["lr"]), mom,
+                                                       float(group["weight_decay"]), 1 if group["nesterov"] else 0,
+                                                       1 if first else 0, float(grad_scale), rec.data_ptr(), rt.stream()),
+                            "hs_sgd_step_multi_clip")
+                else:
+                    L.check(lib.hs_sgd_step_multi(n, arr(sel), arr([p.grad for p in sel]), bufs, cnt, float(group["lr"]), mom,
+                                                  float(group["weight_decay"]), 1 if group["nesterov"] else 0, 1 if first else 0,
+                                                  float(grad_scale), rt.stream()), "hs_sgd_step_multi")
                 rt.shadows_stale(sel)      # this kernel does not write the bf16 weight shadows: the next forward re-casts them
         return loss
