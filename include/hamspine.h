@@ -1009,7 +1009,7 @@ hs_status hs_bert_layer_bwd(const hs_bert_layer_desc* d, const void* x, const vo
 /* ------------------------------------------------------------------------------------------- */
 /* sizeof of ABI struct number `which` as the library was compiled: 0 hs_conv_geom, 1 hs_gemm_params, 2 hs_bn_params,
    3 hs_bn_bwd_params, 4 hs_attn_desc, 5 hs_conv_bn, 6 hs_resblock_desc, 7 hs_stem_desc, 8 hs_linear, 9 hs_norm,
-   10 hs_bert_layer_desc, 11 hs_resnet_desc, 12 hs_resnet_plan, 13 hs_bert_desc; -1 for an unknown number.  A binding
+   10 hs_bert_layer_desc, 11 hs_resnet_desc, 12 hs_resnet_plan, 13 hs_bert_desc, 14 hs_jpeg_info; -1 for an unknown number.  A binding
    (the ctypes mirror in hamspine/_lib.py, a reference-side stub) checks its own declarations against it. */
 int64_t hs_abi_sizeof(int32_t which);
 
@@ -1192,6 +1192,60 @@ hs_status hs_metrics_auroc(const float* scores, const int32_t* labels, int64_t n
    defined classes.  counts == NULL: every AUROC is NaN.  Replaces the torchmetrics .compute() calls of pl_model_MOE2.py:169-171
    and the sklearn calls of ConNexT/models/test.py:112-130, scripts/train.py:121-129. */
 hs_status hs_metrics_finalize(const int64_t* cm, const int64_t* counts, int32_t C, double* out, void* stream);
+
+/* JPEG decode, split where it stops being serial (csrc/jpeg_host.h, csrc/jpeg.hip): DataLoader workers run the Huffman stage on
+   the host and hand over quantised coefficients; dequantisation, the inverse DCT, chroma upsampling, YCbCr -> RGB and the copy
+   into the pack are two kernels per batch.  The arithmetic is libjpeg's default path (the "islow" integer IDCT, "fancy" h2v1 /
+   h2v2 upsampling, 16-bit colour tables; tests/jpeg_ref.py restates it), so the pixels equal Pillow's
+   Image.open(path).convert("RGB") bit for bit.  Replaces the PIL decode of reference data_loader.py:258,274,285,
+   mibf_net/dataset_spine.py:78-80 and ConNexT/dataset/pl_datset.py:136.
+
+   Accepted: SOF0 and 8-bit SOF1 Huffman files with one interleaved scan, 1 component, or 3 components with luma 1x1, 2x1 or 2x2
+   over 1x1 chroma (with a JFIF marker, or without an Adobe marker and with component ids other than 'R','G','B'), of fewer than
+   2^31 output bytes (3 * h * w; HS_JPEG_ERR_TOO_LARGE otherwise: the device stage indexes bytes in 32 bits).  Everything else is
+   refused with its own status and nothing is written; a damaged stream is HS_JPEG_ERR_CORRUPT. */
+enum { HS_JPEG_ERR_CORRUPT = 16, HS_JPEG_ERR_PROGRESSIVE = 17, HS_JPEG_ERR_ARITHMETIC = 18, HS_JPEG_ERR_PROCESS = 19,
+       HS_JPEG_ERR_PRECISION = 20, HS_JPEG_ERR_QTAB16 = 21, HS_JPEG_ERR_COMPONENTS = 22, HS_JPEG_ERR_SAMPLING = 23,
+       HS_JPEG_ERR_MULTISCAN = 24, HS_JPEG_ERR_COLORSPACE = 25, HS_JPEG_ERR_NARROW = 26, HS_JPEG_ERR_TOO_LARGE = 27 };
+#define HS_JPEG_MAX_COMPONENTS 3
+typedef struct hs_jpeg_info {
+    int32_t width, height, components;               /* components: 1 (gray) or 3 (YCbCr)                               */
+    int32_t h_samp[HS_JPEG_MAX_COMPONENTS], v_samp[HS_JPEG_MAX_COMPONENTS];          /* 1 x 1 for a 1-component file     */
+    int32_t block_rows[HS_JPEG_MAX_COMPONENTS], block_cols[HS_JPEG_MAX_COMPONENTS];  /* 8x8 blocks, padded to whole MCUs */
+    int32_t restart_interval;
+    int64_t coef_bytes;                              /* sum over components of block_rows * block_cols * 64 * 2          */
+} hs_jpeg_info;
+/* the text of a status of the two host entries below (a static string; "" for HS_OK) */
+const char* hs_jpeg_status_text(hs_status status);
+/* Host only, no HIP call, no global state, re-entrant: safe in a worker process that must never open the GPU.
+   probe: reads the markers up to the first scan and fills `info`; HS_OK, a refusal or HS_JPEG_ERR_CORRUPT.
+   entropy_decode: as probe, then zeroes `coef` and writes, per component one after another, int16 [block_rows][block_cols][64]
+   quantised coefficients in natural (row-major) order, and qtab[c][64], component c's 8-bit quantisation table in natural
+   order.  coef_bytes below info->coef_bytes is HS_ERR_ARG.  Never reads or writes out of bounds and always consumes input:
+   a truncated file, a bad marker length, a Huffman code outside its table, a run past index 63, a DC category above 11 or an
+   AC category above 10, a DC predictor that leaves int16, a missing or wrong RSTn and a missing table are all
+   HS_JPEG_ERR_CORRUPT (the buffers may then be partly written).  Bytes after the last MCU are not looked at.
+   A coded block takes at least 2 bits (a DC and an AC symbol), so a frame whose blocks cannot fit in the bytes behind SOS is
+   corrupt already for probe, before anyone sizes a buffer from its header: a short file cannot ask for gigabytes. */
+hs_status hs_jpeg_probe(const uint8_t* data, int64_t nbytes, hs_jpeg_info* info);
+hs_status hs_jpeg_entropy_decode(const uint8_t* data, int64_t nbytes, int16_t* coef, int64_t coef_bytes, uint16_t* qtab,
+                                 hs_jpeg_info* info);
+/* Device stage.  HOST tables, checked before any launch, one row per image:
+     geom[i][HS_JPEG_GEOM]  height, width (3 * h * w < 2^31), components, luma h_samp, luma v_samp, 0, 0, 0 (chroma is 1 x 1)
+     coef_off / coef_len    byte offset (16-byte aligned) and length of image i inside the DEVICE arena `coef`; the length must be
+                            what the geometry implies
+     out_off                byte offset of image i's [h][w][3] u8 pixels inside the DEVICE arena `out` (pack_images' layout: any
+                            alignment); ascending, not overlapping.  Bytes of `out` that belong to no image are not written.
+   qtab: DEVICE uint16 [n][3][64].  ws: hs_jpeg_ws_bytes (-1 on a bad table), 16-byte aligned: the padded u8 planes.
+   Two launches per HS_JPEG_CHUNK images (the checked image records travel in the kernels' arguments, as hs_augment_plan's do, so
+   there is no table copy to order on the stream; a batch above HS_JPEG_CHUNK images takes a launch pair per chunk): dequantise + IDCT (one thread per block), then upsample + colour + pack (one thread
+   per aligned 4 output bytes).  No atomics; bitwise repeatable. */
+#define HS_JPEG_GEOM 8
+#define HS_JPEG_CHUNK 32
+int64_t hs_jpeg_ws_bytes(const int32_t* geom, int32_t n);
+hs_status hs_jpeg_decode(const int16_t* coef, int64_t coef_bytes, const uint16_t* qtab, const int32_t* geom,
+                         const int64_t* coef_off, const int64_t* coef_len, const int64_t* out_off, int32_t n, uint8_t* out,
+                         int64_t out_bytes, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

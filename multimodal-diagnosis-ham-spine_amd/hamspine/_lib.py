@@ -27,7 +27,7 @@ class HamspineError(RuntimeError):
 # ------------------------------------------------------------------------------------------ the header, parsed
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "hs_status": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
             "float": C.c_float}
-_POINTEES = {"void", "char", "double", "uint8_t", *_SCALARS}
+_POINTEES = {"void", "char", "double", "uint8_t", "int16_t", "uint16_t", *_SCALARS}
 
 Header = collections.namedtuple("Header", "constants structs prototypes")
 
@@ -163,18 +163,28 @@ _STRUCT_NAMES = {
     "hs_resnet_plan": "ResnetPlan",
     "hs_bert_desc": "BertDesc",
 }
-if set(_header.structs) != set(_STRUCT_NAMES):
-    raise HamspineError(f"{HEADER_PATH}: structs without a Python name, or the reverse: {set(_header.structs) ^ set(_STRUCT_NAMES)}")
+# structs numbered after those (hs_abi_sizeof knows them; abi_structs() keeps listing the descriptor structs above)
+_LATER_STRUCT_NAMES = {
+    "hs_jpeg_info": "JpegInfo",
+}
+_ALL_STRUCT_NAMES = {**_STRUCT_NAMES, **_LATER_STRUCT_NAMES}
+if set(_header.structs) != set(_ALL_STRUCT_NAMES):
+    raise HamspineError(f"{HEADER_PATH}: structs without a Python name, or the reverse: {set(_header.structs) ^ set(_ALL_STRUCT_NAMES)}")
 _classes = {}
 for _c, _fields in _header.structs.items():
-    _classes[_c] = type(_STRUCT_NAMES[_c], (C.Structure,), {"_fields_": [
+    _classes[_c] = type(_ALL_STRUCT_NAMES[_c], (C.Structure,), {"_fields_": [
         (f, _ctype(t, _classes, False) * n if n else _ctype(t, _classes, False)) for f, t, n in _fields]})
-globals().update({_STRUCT_NAMES[_c]: _cls for _c, _cls in _classes.items()})
+globals().update({_ALL_STRUCT_NAMES[_c]: _cls for _c, _cls in _classes.items()})
 
 
 def abi_structs():
     """(number for hs_abi_sizeof, ctypes mirror) of every struct of the C ABI"""
     return list(enumerate(_classes[c] for c in _STRUCT_NAMES))
+
+
+def later_abi_structs():
+    """the same for the structs numbered after the descriptor structs (hs_abi_sizeof 14 and up)"""
+    return list(enumerate((_classes[c] for c in _LATER_STRUCT_NAMES), start=len(_STRUCT_NAMES)))
 
 
 def _const(*names):
@@ -183,6 +193,7 @@ def _const(*names):
 
 if _const("OK") != [HS_OK]:
     raise HamspineError("HS_OK of the header is not 0")
+HS_ERR_ARG, HS_ERR_HIP, HS_ERR_UNSUPPORTED = _const("ERR_ARG", "ERR_HIP", "ERR_UNSUPPORTED")
 HS_F32, HS_BF16 = _const("F32", "BF16")
 A_KC, A_RC, A_CONV, A_DGRAD = _const("A_KC", "A_RC", "A_CONV", "A_DGRAD")
 B_KC, B_RC, B_WDGRAD, B_CONV = _const("B_KC", "B_RC", "B_WDGRAD", "B_CONV")
@@ -191,6 +202,9 @@ MUL_NONE, MUL_GELU_GRAD, MUL_RELU_MASK = _const("MUL_NONE", "MUL_GELU_GRAD", "MU
 CAST_MAX, ADAM_MAX, MUON_MAX, MUON_PARTIALS = _const("CAST_MAX", "ADAM_MAX", "MUON_MAX", "MUON_PARTIALS")
 GRADCLIP_MAX, = _const("GRADCLIP_MAX")
 RESNET_MAX_BLOCKS, RESNET_MAX_TAPS, BERT_MAX_LAYERS = _const("RESNET_MAX_BLOCKS", "RESNET_MAX_TAPS", "BERT_MAX_LAYERS")
+JPEG_GEOM, JPEG_CHUNK, JPEG_MAX_COMPONENTS = _const("JPEG_GEOM", "JPEG_CHUNK", "JPEG_MAX_COMPONENTS")
+# {status: name without HS_JPEG_ERR_} of the JPEG host stage's refusals and of "corrupt"
+JPEG_STATUS = {v: k[len("HS_JPEG_ERR_"):] for k, v in _header.constants.items() if k.startswith("HS_JPEG_ERR_")}
 
 # ------------------------------------------------------------------------------------------ the library
 _lib = None

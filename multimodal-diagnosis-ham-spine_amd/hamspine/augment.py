@@ -1,7 +1,8 @@
 """Device-side image augmentation: the loaders' PIL transforms as HIP kernels (csrc/augment.hip).
 
 The reference's `DataLoader` workers run RandomResizedCrop, flips, RandomRotation and ColorJitter (train) or Resize +
-CenterCrop (eval) per image in PIL, then ToTensor + Normalize.  Here the workers only decode: a collate function packs the
+CenterCrop (eval) per image in PIL, then ToTensor + Normalize.  Here the workers only decode (or, with
+`hamspine.jpeg`, run only the Huffman stage of the decode and leave the rest to `jpeg.decode_pack`): a collate function packs the
 raw `uint8` HWC images of whatever size into one byte arena (`pack_images`), `BatchStager` moves the pack to the device, and
 `TrainTransform` / `EvalTransform` turn it into the `(N, 3, S, S)` f32 batch on the current stream.  The kernels restate
 Pillow's arithmetic exactly (tests/augment_ref.py is the numpy form, pinned against Pillow by tests/gen_augment_golden.py), so

@@ -2410,6 +2410,7 @@ int64_t hs_abi_sizeof(int32_t which) {
         case 11: return sizeof(hs_resnet_desc);
         case 12: return sizeof(hs_resnet_plan);
         case 13: return sizeof(hs_bert_desc);
+        case 14: return sizeof(hs_jpeg_info);
     }
     return -1;
 }
