@@ -811,6 +811,52 @@ hs_status hs_kan_pack_weight(const float* base_w, const float* spline_w, const f
                              int32_t in_f, int32_t nb, void* stream);
 hs_status hs_kan_unpack_wgrad(const float* dwcat, const float* spline_w, const float* scaler, float* d_base, float* d_spline,
                               float* d_scaler, int32_t out_f, int32_t in_f, int32_t nb, void* stream);
+/* KAN grid update on the device (csrc/kan_grid.hip): KANLinear.update_grid without a host round trip, a sort, the
+   (batch, in, out) tensor of per-feature spline outputs or a vendor solver.  f32 in, f32 out; nk = grid_size + 2*order + 1
+   knots and nb = grid_size + order coefficients per feature; every (grid_size >= 1, order >= 0) with nk <= 32 is supported.
+
+   hs_kan_grid_knots: the knot rows grid (in_f, nk) of the batch x (B, in_f), replacing the sort and the knot arithmetic of
+   reference ConNexT/models/block/kan1.py:167-214 (lines 182-211).  Per feature: the order statistics of its column at the
+   0-based positions ranks[0..grid_size] (a HOST array: torch.linspace(0, B-1, grid_size+1, dtype=int64), so the truncation
+   is torch's by construction), its minimum and maximum, then in f32 with every operation rounded on its own and in the
+   reference's order
+       step = (max - min + 2*margin) / grid_size
+       knot[order + j] = grid_eps * (j*step + min - margin) + one_minus_eps * statistic[j]          j = 0..grid_size
+       knot[order - m] = knot[order] - step*m,  knot[order + grid_size + m] = knot[order + grid_size] + step*m     m = 1..order
+   The statistics are the values torch.sort gives: equal values and +-0.0 compare equal (a selected zero is written as
+   +0.0), a NaN sorts last.  A column does not influence another column's knots.  The selection is a radix select with integer
+   counts (no atomics): a rerun repeats bitwise.  ws: hs_kan_grid_knots_ws_bytes() bytes -- 0 today (the counters live in
+   LDS; ws may then be NULL), -1 for arguments the entry refuses.
+   Refused before any launch (HS_ERR_ARG): x, ranks or grid NULL; B < 1; in_f < 1; an unsupported knot count; ws_bytes below
+   hs_kan_grid_knots_ws_bytes(); a rank outside [0, B). */
+int64_t hs_kan_grid_knots_ws_bytes(int64_t B, int32_t in_f, int32_t grid_size, int32_t order);
+hs_status hs_kan_grid_knots(const float* x, const int64_t* ranks, float* grid, int64_t B, int32_t in_f, int32_t grid_size,
+                            int32_t order, float grid_eps, float one_minus_eps, float margin, void* ws, int64_t ws_bytes,
+                            void* stream);
+/* hs_kan_refit: per-feature least-squares fit of spline coefficients on the knots grid_new (in_f, nk), replacing the batched
+   torch.linalg.lstsq of reference kan1.py:112-142 (curve2coeff) and, in S-mode, the spline-output tensor of
+   kan1.py:167-214 (lines 172-179, 214) as well.  With A_i (B x nb) the bases of x[:, i] on grid_new:
+     S-mode (grid_old and spline_w given, y NULL): S_i = the bases on grid_old (in_f, nk), C_i[q][o] = spline_w[o][i][q] *
+       scaler[o][i] (scaler NULL = 1; the product is rounded to f32 as the reference's scaled_spline_weight is), and
+       out[o][i][:] = (A_i^+ S_i) C_i[:, o] -- the minimiser of |A_i sol - S_i C_i|, i.e. update_grid's fit;
+     y-mode (y (B, in_f, out_f) given, grid_old and spline_w NULL): out[o][i][:] = A_i^+ y[:, i, o], i.e. curve2coeff.
+   The bases come from the evaluation hs_kan_features_fwd uses.  A_i^T A_i and A_i^T S_i (or A_i^T Y_i) are summed in f64,
+   one workspace slot per chunk of 256 rows, and the slots are added in chunk order: no atomics, a rerun repeats bitwise.
+   A_i^+ = V diag(1/lambda) V^T A_i^T from a cyclic Jacobi eigen-decomposition of the Gram matrix in f64 (at most 24 sweeps),
+   with the eigenvalues <= rcond^2 * lambda_max dropped, rcond = 2^-23 * max(B, nb): the default cutoff of torch.linalg.lstsq,
+   applied to the squared singular values.  A feature of full column rank gets the least-squares solution; a rank-deficient
+   one (a constant column, B < nb, ...) gets the truncated pseudo-inverse solution, the least-norm one among the minimisers
+   (the reference's drivers are undefined or unbounded there).  out is (out_f, in_f, nb) like spline_w and may alias it.  The
+   result is NOT divided by the scaler (kan1.py:214).  A feature's result depends on its own column alone.
+   ws: hs_kan_refit_ws_bytes() = ceil(B/256) * in_f * nb * (nb + (y_mode ? out_f : nb)) doubles, 8-byte aligned; -1 for
+   arguments the entry refuses.
+   Refused before any launch (HS_ERR_ARG): x, grid_new, out or ws NULL; B < 1; in_f or out_f < 1; an unsupported knot count;
+   both or neither of S-mode (grid_old / spline_w) and y-mode (y); S-mode with only one of grid_old, spline_w; ws_bytes below
+   hs_kan_refit_ws_bytes(); a misaligned ws. */
+int64_t hs_kan_refit_ws_bytes(int64_t B, int32_t in_f, int32_t out_f, int32_t grid_size, int32_t order, int32_t y_mode);
+hs_status hs_kan_refit(const float* x, const float* grid_new, const float* grid_old, const float* y, const float* spline_w,
+                       const float* scaler, float* out, int64_t B, int32_t in_f, int32_t out_f, int32_t grid_size, int32_t order,
+                       void* ws, int64_t ws_bytes, void* stream);
 /* noisy top-k gating on clean = x@w_gate (and raw_noise = x@w_noise when noisy): gates (B,E), load-balancing loss
    coef*(cv^2(importance)+cv^2(load)), plus everything the backward needs (p, top: (B,17) int32, z, sigma,
    loadrow, d_imp[E], d_load[E]).  E <= 16.

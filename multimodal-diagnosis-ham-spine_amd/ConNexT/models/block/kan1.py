@@ -1,5 +1,6 @@
 """KANLinear / KAN1 (reference ConNexT/models/block/kan1.py) with the same parameters (base_weight, spline_weight,
-spline_scaler), buffer (grid) and initialisation; the forward/backward run on the hamspine kernels in f32."""
+spline_scaler), buffer (grid) and initialisation; the forward/backward and, for a module on the GPU, update_grid / curve2coeff
+run on the hamspine kernels in f32."""
 import math
 import types
 
@@ -47,10 +48,18 @@ class KANLinear(torch.nn.Module):
             bases = left + right
         return bases.contiguous()
 
-    def curve2coeff(self, x, y):
+    def _curve2coeff_host(self, x, y):
         A = self._b_splines_host(x).transpose(0, 1)
         sol = torch.linalg.lstsq(A, y.transpose(0, 1)).solution
         return sol.permute(2, 0, 1).contiguous()
+
+    def curve2coeff(self, x, y):
+        """kan1.py:112-142.  GPU tensors are fitted by the device kernels (hs_kan_refit, no vendor solver); a module that still
+        lives on the CPU (reset_parameters) keeps the host code."""
+        if self.grid.is_cuda:
+            assert x.dim() == 2 and x.size(1) == self.in_features and y.size() == (x.size(0), self.in_features, self.out_features)
+            return K.kan_curve2coeff(x.float(), y.float(), self.grid, self.grid_size, self.spline_order)
+        return self._curve2coeff_host(x, y)
 
     def reset_parameters(self):
         torch.nn.init.kaiming_uniform_(self.base_weight, a=math.sqrt(5) * self.scale_base)
@@ -78,12 +87,26 @@ class KANLinear(torch.nn.Module):
 
     @torch.no_grad()
     def update_grid(self, x, margin=0.01):
-        """Data-dependent re-gridding (reference kan1.py:167-212): the knots move to the batch's per-feature quantiles
+        """Data-dependent re-gridding (reference kan1.py:167-214): the knots move to the batch's per-feature quantiles
         (blended with a uniform grid by grid_eps) and the spline coefficients are re-fitted by least squares so that the
-        spline part reproduces its old outputs on x.  A maintenance step between batches, not part of the per-batch path:
-        like reset_parameters it runs on the host in f32 (sort + a batched least-squares solve of `in_features` small systems)
-        and writes the results back into the device-resident buffers the kernels read."""
+        spline part reproduces its old outputs on x.  With the buffers on the GPU this runs on the device kernels
+        (hamspine.kan.kan_update_grid: quantile select, f64 normal equations, Jacobi pseudo-inverse) and writes the grid buffer
+        and spline_weight.data in place on the current stream, with no host round trip; a module on the CPU keeps the host
+        code below."""
         assert x.dim() == 2 and x.size(1) == self.in_features
+        if not self.grid.is_cuda:
+            return self._update_grid_host(x, margin)
+        x = x.detach()
+        if x.dtype != torch.float32:
+            x = x.float()
+        scaler = self.spline_scaler.data if self.enable_standalone_scale_spline else None
+        K.kan_update_grid(x, self.grid, self.spline_weight.data, scaler, self.grid_size, self.spline_order, self.grid_eps, margin)
+
+    @torch.no_grad()
+    def _update_grid_host(self, x, margin=0.01):
+        """update_grid in f32 on the host (sort + a batched LAPACK least-squares solve of `in_features` small systems over the
+        (batch, in, out) tensor of per-feature spline outputs), written back into the buffers wherever they live: the code of a
+        CPU module, and the route tools/kan_grid_bench.py times the device kernels against."""
         dev = self.grid.device
         xh = x.detach().float().cpu()
         batch = xh.size(0)

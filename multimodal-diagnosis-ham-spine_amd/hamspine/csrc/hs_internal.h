@@ -1,6 +1,7 @@
 // Functions that one file of the library defines and another calls, outside the C ABI.  The defining files (gemm.hip, norm.hip,
 // elem.hip, attn_fused.hip) include this header as well as the callers, so a drifted signature does not compile, and the link
-// refuses undefined symbols (-z defs).  Default arguments are stated here only.
+// refuses undefined symbols (-z defs).  Default arguments are stated here only.  At the end: the one device function two files
+// share (the B-spline evaluation of the KAN forward and of the KAN grid update).
 #pragma once
 #include "hs_common.h"
 
@@ -72,5 +73,30 @@ int bert_embed_fwd_rows(int dtype, const int64_t* ids, const float* word, const 
                         float eps, float dropout_p, unsigned long long seed, const int* nrows, const int* row_of, hipStream_t stream);
 int bert_embed_bwd_rows(int dtype, const int64_t* ids, const void* dsum, float* dword, float* dpos, int B, int L, int H, int V,
                         int pad_id, const int* nrows, const int* row_of, const int* packed_of, hipStream_t s);
+
+// ---- kan_moe.hip, kan_grid.hip (device) ----
+constexpr int KAN_MAXK = 32;   // knots per feature: grid_size + 2*order + 1 <= 32
+
+// Cox-de Boor recursion exactly as kan1.py:92-103, carried in forward mode so the derivative equals what
+// autograd produces for that formula: B (and dB/dx) of order `order`, nb = G + order values.  The forward, its backward and
+// the re-fit of kan_grid.hip all evaluate their bases here, so a fit sees the values the forward produces.
+__device__ __forceinline__ void bspline_eval(float x, const float* __restrict__ g, int nk, int order, float* B, float* dB) {
+    const int n0 = nk - 1;
+    for (int j = 0; j < n0; ++j) {
+        B[j] = (x >= g[j] && x < g[j + 1]) ? 1.f : 0.f;
+        dB[j] = 0.f;
+    }
+    for (int k = 1; k <= order; ++k) {
+        const int n = n0 - k;
+        for (int j = 0; j < n; ++j) {
+            const float d1 = g[j + k] - g[j], d2 = g[j + k + 1] - g[j + 1];
+            const float a = (x - g[j]) / d1, c = (g[j + k + 1] - x) / d2;
+            const float nb = a * B[j] + c * B[j + 1];
+            const float nd = B[j] / d1 + a * dB[j] - B[j + 1] / d2 + c * dB[j + 1];
+            B[j] = nb;
+            dB[j] = nd;
+        }
+    }
+}
 
 }  // namespace hs

@@ -3,36 +3,13 @@
 // ([SiLU(x) | bases] x [base_weight | scaled spline weight]) run on the MFMA GEMM core (hs_gemm, f32).
 // Also: supervised-contrastive loss (reference scripts/train.py:23-44).
 #include <algorithm>
-#include "hs_common.h"
+#include "hs_internal.h"   // KAN_MAXK, bspline_eval (shared with kan_grid.hip)
 
 namespace hs {
-
-constexpr int KAN_MAXK = 32;   // knots per feature: grid_size + 2*order + 1 <= 32
 
 static inline int grid_for(long long n, int cap = 2048) {
     long long b = (n + 255) / 256;
     return (int)std::max<long long>(1, std::min<long long>(b, cap));
-}
-
-// Cox-de Boor recursion exactly as kan1.py:92-103, carried in forward mode so the derivative equals what
-// autograd produces for that formula: B (and dB/dx) of order `order`, nb = G + order values.
-__device__ __forceinline__ void bspline_eval(float x, const float* __restrict__ g, int nk, int order, float* B, float* dB) {
-    const int n0 = nk - 1;
-    for (int j = 0; j < n0; ++j) {
-        B[j] = (x >= g[j] && x < g[j + 1]) ? 1.f : 0.f;
-        dB[j] = 0.f;
-    }
-    for (int k = 1; k <= order; ++k) {
-        const int n = n0 - k;
-        for (int j = 0; j < n; ++j) {
-            const float d1 = g[j + k] - g[j], d2 = g[j + k + 1] - g[j + 1];
-            const float a = (x - g[j]) / d1, c = (g[j + k + 1] - x) / d2;
-            const float nb = a * B[j] + c * B[j + 1];
-            const float nd = B[j] / d1 + a * dB[j] - B[j + 1] / d2 + c * dB[j + 1];
-            B[j] = nb;
-            dB[j] = nd;
-        }
-    }
 }
 
 // base activation of the layer (kan1.py:17 `base_activation`, SiLU by default; the KAN classifier head of

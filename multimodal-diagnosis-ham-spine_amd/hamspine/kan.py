@@ -1,7 +1,7 @@
 """KAN layer, mixture-of-experts gating and SupCon loss on the HIP kernels (csrc/kan_moe.hip + hs_gemm, f32).
 
 reference: ConNexT/models/block/kan1.py:77-165 (KANLinear.forward / b_splines), moe.py:171-291 (MoE),
-scripts/train.py:23-44 (SupConLoss).
+scripts/train.py:23-44 (SupConLoss); kan1.py:167-214 / :112-142 (update_grid / curve2coeff, csrc/kan_grid.hip).
 """
 import ctypes as C
 
@@ -81,6 +81,62 @@ class KANLinearFn(Function):
 def kan_linear(x, grid, base_weight, spline_weight, spline_scaler, grid_size, spline_order, base_act="silu"):
     return KANLinearFn.apply(x, grid, base_weight, spline_weight, spline_scaler, int(grid_size), int(spline_order),
                              BASE_ACTS[base_act])
+
+
+def _refit(x, grid_new, grid_old, y, spline_weight, spline_scaler, out, grid_size, order):
+    lib = L.lib()
+    B, in_f = x.shape
+    out_f = out.shape[0]
+    nbytes = lib.hs_kan_refit_ws_bytes(B, in_f, out_f, grid_size, order, 1 if y is not None else 0)
+    if nbytes < 0:
+        raise L.HamspineError(f"kan refit: unsupported shape B={B} in={in_f} out={out_f} grid_size={grid_size} order={order}")
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=x.device)
+    L.check(lib.hs_kan_refit(rt.p(x), rt.p(grid_new), rt.p(grid_old), rt.p(y), rt.p(spline_weight), rt.p(spline_scaler), rt.p(out),
+                             B, in_f, out_f, grid_size, order, rt.p(ws), nbytes, rt.stream()), "hs_kan_refit")
+
+
+def _param_f32(t, what):
+    """a parameter or buffer the kernels write in place: it has to be the f32 contiguous storage itself, never a copy"""
+    rt.need_gpu(t)
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise L.HamspineError(f"{what}: expected a contiguous f32 tensor, got {t.dtype}, strides {t.stride()}")
+    return t
+
+
+@torch.no_grad()
+def kan_update_grid(x, grid, spline_weight, spline_scaler, grid_size, spline_order, grid_eps=0.02, margin=0.01):
+    """KANLinear.update_grid (reference kan1.py:167-214) on the device: `grid` (in, knots) moves to the per-feature quantiles of
+    x (B, in) blended with a uniform grid, and `spline_weight` (out, in, coeffs) is re-fitted so that the spline part keeps its
+    outputs on x.  Both are written in place on the current stream; nothing comes back to the host.  spline_scaler (out, in) or
+    None.  A rank-deficient feature gets the least-norm least-squares solution (see hs_kan_refit)."""
+    x = _f32c(x.detach())
+    grid, spline_weight = _param_f32(grid, "grid"), _param_f32(spline_weight, "spline_weight")
+    spline_scaler = _f32c(spline_scaler.detach()) if spline_scaler is not None else None
+    grid_size, order = int(grid_size), int(spline_order)
+    B, in_f = x.shape
+    if B < 1:
+        raise L.HamspineError("kan_update_grid: an empty batch has no quantiles")
+    lib = L.lib()
+    ranks = torch.linspace(0, B - 1, grid_size + 1, dtype=torch.int64)       # host: the reference's own index arithmetic
+    new_grid = torch.empty_like(grid)
+    L.check(lib.hs_kan_grid_knots(rt.p(x), ranks.data_ptr(), rt.p(new_grid), B, in_f, grid_size, order, grid_eps, 1 - grid_eps,
+                                  margin, None, 0, rt.stream()), "hs_kan_grid_knots")
+    _refit(x, new_grid, grid, None, spline_weight, spline_scaler, spline_weight, grid_size, order)
+    grid.copy_(new_grid)
+
+
+@torch.no_grad()
+def kan_curve2coeff(x, y, grid, grid_size, spline_order):
+    """KANLinear.curve2coeff (reference kan1.py:112-142) on the device: the coefficients (out, in, coeffs) whose splines on the
+    knots `grid` (in, knots) fit y (B, in, out) at x (B, in) in the least-squares sense, per input feature."""
+    x, y, grid = _f32c(x.detach()), _f32c(y.detach()), _f32c(grid.detach())
+    grid_size, order = int(grid_size), int(spline_order)
+    B, in_f = x.shape
+    if y.dim() != 3 or y.shape[0] != B or y.shape[1] != in_f:
+        raise L.HamspineError(f"kan_curve2coeff: y {tuple(y.shape)} is not (batch, in, out) = ({B}, {in_f}, out)")
+    out = torch.empty((y.shape[2], in_f, grid_size + order), dtype=torch.float32, device=x.device)
+    _refit(x, grid, None, y, None, None, out, grid_size, order)
+    return out
 
 
 class MoEGateFn(Function):
