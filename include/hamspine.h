@@ -758,6 +758,31 @@ hs_status hs_supcon_loss(const float* feat, const int64_t* labels, int32_t B, in
                          float* dfeat, float* ws, void* stream);
 int64_t hs_supcon_ws_bytes(int32_t B, int32_t D);
 
+/* The same loss over any number of rows, tiled on the f32-input MFMA (csrc/supcon.hip), for one process or for W ranks that
+   have gathered the step's N = W * B rows.  `loss` is SupConLoss(temperature) over ALL N rows with the reference's constants:
+   rows normalised by max(norm, 1e-12); row maximum over all j, the diagonal included; E_i = 1e-8 + sum_{j != i} exp(s_ij - mx_i)
+   (the 1e-8 joins after the last online-softmax rescale); denominators P_i + 1e-8; mean over the N anchors.  `dfeat` (optional,
+   [M][D]) is grad_scale * d loss / d feat for the rows row0 .. row0 + M - 1 only, the rows the caller owns; it contains the
+   terms of the anchors outside those rows.  One process passes row0 = 0, M = N, grad_scale = 1.  An anchor without positives
+   adds exactly 0 to the loss and to the gradient; a zero-norm row is treated as by hs_supcon_loss.
+   Range: 1 <= N <= HS_SUPCON_TILED_MAX_N, 1 <= D <= HS_SUPCON_TILED_MAX_D, 0 <= row0, 1 <= M, row0 + M <= N.  Anything else,
+   a NULL feat / labels / loss / ws, or a ws that is not 16-byte aligned is refused (HS_ERR_ARG) before anything is written.
+   ws: hs_supcon_tiled_ws_bytes(N, D) = 4 * (N * Dp + 6 * N + [KS > 1] KS * N * (Dp + 5)) bytes, Dp = D rounded up to a
+   multiple of 4: the normalised copy, which is the only copy of the features; six floats per row (norm, maximum, E, P,
+   weight, the row's loss); and, where the keys are cut into KS > 1 runs so that a pass fills the device, the runs' partial
+   results per row.  NT = ceil(N / 64) key tiles, want = min(NT, 16, ceil(512 / NT)), tps = ceil(NT / want) tiles per run,
+   KS = ceil(NT / tps) <= 16: 1 for N <= 64 and for N > 32768, so the workspace stays below 17 N Dp + 86 N floats and has no
+   N^2 term.  -1 for (N, D) outside the range.  The size of ws is not checked.  No N x N array exists.  No atomics: every sum
+   has one order that depends on (N, D) alone (KS never depends on row0 or M), so a rerun repeats bitwise, and the rows of a
+   sliced call equal those rows of the full call bitwise (so do the losses).  f32 throughout: s_ij is one fma chain of Dp
+   terms, d fn_i one fma chain of up to 64 * tps terms per run and KS - 1 additions.  Four to six launches, no host
+   synchronisation.  No reference counterpart for N > its batch: it is the reference's loss on the concatenated batch. */
+#define HS_SUPCON_TILED_MAX_N 65536
+#define HS_SUPCON_TILED_MAX_D 4096
+int64_t hs_supcon_tiled_ws_bytes(int32_t N, int32_t D);
+hs_status hs_supcon_tiled(const float* feat, const int64_t* labels, int32_t N, int32_t D, int32_t row0, int32_t M,
+                          float temperature, float grad_scale, float* loss, float* dfeat, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------- */
 /* ConvNeXt operators on NHWC activations (reference ConNexT/models/ourmodel.py:43,78 ->          */
 /* transformers ConvNextModel: ConvNextLayer.dwconv / layer_scale_parameter, ConvNextEmbeddings   */

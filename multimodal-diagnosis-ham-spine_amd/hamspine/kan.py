@@ -1,4 +1,5 @@
-"""KAN layer, mixture-of-experts gating and SupCon loss on the HIP kernels (csrc/kan_moe.hip + hs_gemm, f32).
+"""KAN layer, mixture-of-experts gating and SupCon loss on the HIP kernels (csrc/kan_moe.hip + hs_gemm, f32; SupCon beyond 256
+rows and over the gathered batch of a process group: csrc/supcon.hip).
 
 reference: ConNexT/models/block/kan1.py:77-165 (KANLinear.forward / b_splines), moe.py:171-291 (MoE),
 scripts/train.py:23-44 (SupConLoss); kan1.py:167-214 / :112-142 (update_grid / curve2coeff, csrc/kan_grid.hip).
@@ -339,8 +340,113 @@ class SupConFn(Function):
         return out, None, None
 
 
-def supcon_loss(features, labels, temperature=0.07):
-    return SupConFn.apply(features, labels, float(temperature))
+def _resolve_group(group):
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        raise L.HamspineError("supcon_loss(group=...): torch.distributed is not initialised")
+    return dist.group.WORLD if isinstance(group, str) and group == "world" else group
+
+
+def _gather_rows(t, pg, world):
+    """rows of every rank, in rank order, without an autograd graph: on the device for nccl, through host memory otherwise"""
+    import torch.distributed as dist
+    shape = (world * t.shape[0],) + tuple(t.shape[1:])
+    if dist.get_backend(pg) == "nccl":
+        out = torch.empty(shape, dtype=t.dtype, device=t.device)
+        dist.all_gather_into_tensor(out, t, group=pg)
+        return out
+    out = torch.empty(shape, dtype=t.dtype)
+    dist.all_gather(list(out.chunk(world)), t.cpu(), group=pg)
+    return out.to(t.device)
+
+
+def _require_equal_batches(B, D, pg, world):
+    """ValueError on EVERY rank when the local (B, D) differ, before any rank enters the gather (so none is left waiting).
+    Host-route backends only: with nccl the check would need a read-back, i.e. a host synchronisation per step, and equal
+    sizes are the caller's contract there, as they are for all_gather_into_tensor itself."""
+    import torch.distributed as dist
+    if dist.get_backend(pg) == "nccl":
+        return
+    sizes = [torch.zeros(2, dtype=torch.int64) for _ in range(world)]
+    dist.all_gather(sizes, torch.tensor([B, D], dtype=torch.int64), group=pg)
+    sizes = [tuple(s.tolist()) for s in sizes]
+    if any(s != sizes[0] for s in sizes):
+        raise ValueError(f"supcon_loss(group=...): every rank must hold the same (batch, dim), got {sizes}")
+
+
+class SupConTiledFn(Function):
+    """hs_supcon_tiled: the loss over all rows (of all ranks of `pg`, if given) and the gradient of this rank's rows, computed
+    together in the forward.  grad_scale multiplies the saved gradient (the world size when the trainer averages)."""
+
+    @staticmethod
+    def forward(ctx, feat, labels, temperature, pg, average_across_ranks):
+        feat = _f32c(feat)
+        labels = labels.contiguous().long()
+        rt.need_gpu(labels)
+        B, D = feat.shape
+        if labels.shape != (B,):
+            raise L.HamspineError(f"supcon_loss: labels {tuple(labels.shape)} for features {tuple(feat.shape)}")
+        row0, scale, allf, alll = 0, 1.0, feat, labels
+        if pg is not None:
+            import torch.distributed as dist
+            world, rank = dist.get_world_size(pg), dist.get_rank(pg)
+            _require_equal_batches(B, D, pg, world)
+            allf, alll = _gather_rows(feat.detach(), pg, world), _gather_rows(labels, pg, world)
+            row0, scale = rank * B, float(world) if average_across_ranks else 1.0
+        N = allf.shape[0]
+        lib = L.lib()
+        nbytes = lib.hs_supcon_tiled_ws_bytes(N, D)
+        if nbytes < 0:
+            raise L.HamspineError(f"supcon_loss: {N} rows of {D} features are outside the tiled kernel's range "
+                                  f"(N <= {L._header.constants['HS_SUPCON_TILED_MAX_N']}, "
+                                  f"D <= {L._header.constants['HS_SUPCON_TILED_MAX_D']})")
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=feat.device)
+        loss = torch.empty((), dtype=torch.float32, device=feat.device)
+        df = torch.empty_like(feat)
+        L.check(lib.hs_supcon_tiled(rt.p(allf), rt.p(alll), N, D, row0, B, temperature, scale, rt.p(loss), rt.p(df), rt.p(ws),
+                                    rt.stream()), "hs_supcon_tiled")
+        ctx.save_for_backward(df)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (df,) = ctx.saved_tensors
+        g = g.contiguous().float()
+        out = torch.empty_like(df)
+        L.check(L.lib().hs_mul_dev_scalar(rt.p(df), rt.p(g), rt.p(out), df.numel(), rt.stream()), "hs_mul_dev_scalar")
+        return out, None, None, None, None
+
+
+def supcon_loss(features, labels, temperature=0.07, *, group=None, tiled=None, average_across_ranks=True):
+    """SupConLoss(temperature) of the reference (scripts/train.py:23-44) with its gradient.
+
+    group=None: the loss of these rows.  Up to 256 rows take the single-workgroup kernel (hs_supcon_loss) unless tiled=True;
+    more rows, or tiled=True, take the tiled MFMA kernels (hs_supcon_tiled).
+    group=<process group> or "world": the loss of the step's GLOBAL batch -- features and labels of all ranks are gathered
+    (equal local batch sizes are required: ValueError), every rank returns the same loss, and each rank's backward yields the
+    gradient of that global loss with respect to its own rows, terms of the other ranks' anchors included.  A contrastive loss
+    is not a sum over ranks: the mean of per-rank losses has other negatives, other positives and another gradient.
+    average_across_ranks=True (default) multiplies that gradient by the world size, for trainers that AVERAGE parameter
+    gradients (hamspine.ddp.DataParallel, torch DDP): after the average every parameter holds exactly the gradient of the
+    global loss.  False leaves the factor 1 (trainers that sum)."""
+    T = float(temperature)
+    if group is not None:
+        return SupConTiledFn.apply(features, labels, T, _resolve_group(group), bool(average_across_ranks))
+    if tiled is True or (tiled is None and features.shape[0] > 256):
+        return SupConTiledFn.apply(features, labels, T, None, False)
+    return SupConFn.apply(features, labels, T)
+
+
+class SupConLoss(torch.nn.Module):
+    """The reference's SupConLoss(temperature=0.07) (scripts/train.py:23-44); group: see supcon_loss."""
+
+    def __init__(self, temperature=0.07, group=None):
+        super().__init__()
+        self.temperature = temperature
+        self.group = group
+
+    def forward(self, features, labels):
+        return supcon_loss(features, labels, self.temperature, group=self.group)
 
 
 class KANRegularizationFn(Function):
