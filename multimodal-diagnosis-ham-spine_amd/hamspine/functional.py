@@ -11,6 +11,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
+from . import desc as DL
 from . import rt
 
 CL = torch.channels_last
@@ -22,24 +23,6 @@ def _lib():
 
 def _cl_weight(w):
     return w if w.is_contiguous(memory_format=CL) else w.contiguous(memory_format=CL)
-
-
-def _fill_cb(cb, geo, w, gamma, beta, rm, rv, dw=None, dgamma=None, dbeta=None):
-    cb.Cin, cb.Cout, cb.R, cb.stride, cb.pad = geo
-    cb.w = rt.p(w)
-    cb.gamma, cb.beta = rt.p(gamma), rt.p(beta)
-    cb.running_mean, cb.running_var = rt.p(rm), rt.p(rv)
-    cb.dw, cb.dgamma, cb.dbeta = rt.p(dw), rt.p(dgamma), rt.p(dbeta)
-
-
-def _lin(in_f, out_f, w, b, dw=None, db=None, w_off=0, b_off=0):
-    l = L.Linear()
-    l.in_f, l.out_f = in_f, out_f
-    l.w = rt.p(w, w_off * 4)
-    l.b = rt.p(b, b_off * 4) if b is not None else None
-    l.dw = rt.p(dw, w_off * 4) if dw is not None else None
-    l.db = rt.p(db, b_off * 4) if db is not None else None
-    return l
 
 
 def _grad_like(t, needed):
@@ -60,27 +43,19 @@ class StemFn(Function):
             image = image.float()
         w = _cl_weight(weight)
         N, Cin, H, W = image.shape
-        d = L.StemDesc()
-        d.dtype = rt.hs_dtype(cfg["dtype"])
-        d.N, d.H, d.W = N, H, W
-        d.training = 1 if cfg["training"] else 0
-        d.eps, d.momentum = cfg["eps"], cfg["momentum"]
-        # no gradient will be asked for (inference under no_grad): BatchNorm folds into the convolution epilogue
-        d.inference = 0 if (cfg["training"] or any(ctx.needs_input_grad)) else 1
         geo = (Cin, weight.shape[0], 7, 2, 3)
-        _fill_cb(d.cb, geo, w, gamma, beta, cfg["running_mean"], cfg["running_var"])
+        d = L.StemDesc()
+        # inference: no gradient will be asked for (eval under no_grad), BatchNorm folds into the convolution epilogue
+        DL.fill_stem(d, rt.hs_dtype(cfg["dtype"]), N, H, W, cfg["training"], cfg["eps"], cfg["momentum"], geo, w, gamma, beta,
+                     cfg["running_mean"], cfg["running_var"], inference=not (cfg["training"] or any(ctx.needs_input_grad)))
         sv_b, ws_b = rt.query(_lib().hs_stem_query, d)
         saved = torch.empty(sv_b, dtype=torch.uint8, device=image.device)
         ws = rt.workspace(ws_b, image.device)
-        P = (H + 6 - 7) // 2 + 1
-        Q = (W + 6 - 7) // 2 + 1
-        P2, Q2 = (P + 2 - 3) // 2 + 1, (Q + 2 - 3) // 2 + 1
-        y = rt.empty_cl((N, weight.shape[0], P2, Q2), cfg["dtype"], image.device)
+        y = rt.empty_cl((N, weight.shape[0], DL.stem_out(H), DL.stem_out(W)), cfg["dtype"], image.device)
         L.check(_lib().hs_stem_fwd(C.byref(d), rt.p(image), rt.p(y), rt.p(saved), sv_b, rt.p(ws), ws.numel(), rt.stream()),
                 "hs_stem_fwd")
         ctx.save_for_backward(image, w, gamma, beta, saved, y)
-        ctx.cfg = cfg
-        ctx.geo = geo
+        ctx.cfg, ctx.geo = cfg, geo
         return y
 
     @staticmethod
@@ -88,65 +63,47 @@ class StemFn(Function):
         image, w, gamma, beta, saved, y = ctx.saved_tensors
         cfg = ctx.cfg
         dy = rt.as_cl(dy, cfg["dtype"])
-        N, Cin, H, W = image.shape
         d = L.StemDesc()
-        d.dtype = rt.hs_dtype(cfg["dtype"])
-        d.N, d.H, d.W = N, H, W
-        d.training = 1 if cfg["training"] else 0
-        d.eps, d.momentum = cfg["eps"], cfg["momentum"]
-        dw = _grad_like(w, ctx.needs_input_grad[1])
-        dg = _grad_like(gamma, ctx.needs_input_grad[2])
-        db = _grad_like(beta, ctx.needs_input_grad[3])
-        _fill_cb(d.cb, ctx.geo, w, gamma, beta, None, None, dw, dg, db)
+        N, _, H, W = image.shape
+        DL.fill_stem(d, rt.hs_dtype(cfg["dtype"]), N, H, W, cfg["training"], cfg["eps"], cfg["momentum"], ctx.geo, w, gamma, beta, None, None)
+        grads = [_grad_like(t, n) for t, n in zip((w, gamma, beta), ctx.needs_input_grad[1:4])]
+        DL.set_grads(d, [rt.p(g) for g in grads])
         sv_b, ws_b = rt.query(_lib().hs_stem_query, d)
         ws = rt.workspace(ws_b, image.device)
         L.check(_lib().hs_stem_bwd(C.byref(d), rt.p(y), rt.p(dy), rt.p(saved), saved.numel(), rt.p(ws), ws.numel(),
                                    rt.stream()), "hs_stem_bwd")
-        return None, dw, dg, db, None
+        return (None, *grads, None)
 
 
 class ResBlockFn(Function):
     """torchvision BasicBlock / Bottleneck as one node (reference encoder.py:69-72, model_resnet.py:15).
 
-    params = [w, gamma, beta] per main conv (2 or 3) followed by the optional downsample triple."""
+    params = [w, gamma, beta] per main conv (2 or 3), then the optional downsample triple; cfg["stages"] = their (geo, running_mean, running_var)"""
 
     @staticmethod
-    def _desc(cfg, x_shape, params, grads=None):
+    def _desc(cfg, x_shape, params, forward=True):
+        """the backward form passes no running statistics; its caller sets the gradients"""
         d = L.ResblockDesc()
-        d.dtype = rt.hs_dtype(cfg["dtype"])
-        d.N, d.H, d.W = x_shape[0], x_shape[2], x_shape[3]
-        d.training = 1 if cfg["training"] else 0
-        d.eps, d.momentum = cfg["eps"], cfg["momentum"]
-        stages = cfg["stages"]
-        n_main = len(stages) - (1 if cfg["has_ds"] else 0)
-        d.n_main = n_main
-        d.has_ds = 1 if cfg["has_ds"] else 0
-        for i, st in enumerate(stages):
-            w, g, b = params[3 * i:3 * i + 3]
-            gr = grads[3 * i:3 * i + 3] if grads is not None else (None, None, None)
-            cb = d.main[i] if i < n_main else d.ds
-            _fill_cb(cb, st["geo"], w, g, b, st["rm"] if grads is None else None, st["rv"] if grads is None else None, *gr)
+        stages = [(geo, *wgb, rm if forward else None, rv if forward else None)
+                  for (geo, rm, rv), wgb in zip(cfg["stages"], DL.conv_bn_triples(params))]
+        DL.fill_resblock(d, rt.hs_dtype(cfg["dtype"]), x_shape[0], x_shape[2], x_shape[3], cfg["training"], cfg["eps"],
+                        cfg["momentum"], stages, cfg["has_ds"])
         return d
 
     @staticmethod
     def forward(ctx, x, cfg, *params):
         rt.need_gpu(x, *params)
         x = rt.as_cl(x, cfg["dtype"])
-        params = list(params)
-        for i in range(0, len(params), 3):
-            params[i] = _cl_weight(params[i])
+        params = [q for w, gamma, beta in DL.conv_bn_triples(params) for q in (_cl_weight(w), gamma, beta)]
         d = ResBlockFn._desc(cfg, x.shape, params)
         d.inference = 0 if (cfg["training"] or any(ctx.needs_input_grad)) else 1
         sv_b, ws_b = rt.query(_lib().hs_resblock_query, d)
         saved = torch.empty(sv_b, dtype=torch.uint8, device=x.device)
         ws = rt.workspace(ws_b, x.device)
-        stages = cfg["stages"]
-        n_main = len(stages) - (1 if cfg["has_ds"] else 0)
         H, W = x.shape[2], x.shape[3]
-        for st in stages[:n_main]:
-            _, _, R, s, pd = st["geo"]
-            H, W = (H + 2 * pd - R) // s + 1, (W + 2 * pd - R) // s + 1
-        y = rt.empty_cl((x.shape[0], stages[n_main - 1]["geo"][1], H, W), cfg["dtype"], x.device)
+        for (_, Cout, R, s, pd), _, _ in cfg["stages"][:d.n_main]:
+            H, W = DL.conv_out(H, R, s, pd), DL.conv_out(W, R, s, pd)
+        y = rt.empty_cl((x.shape[0], Cout, H, W), cfg["dtype"], x.device)
         L.check(_lib().hs_resblock_fwd(C.byref(d), rt.p(x), rt.p(y), rt.p(saved), sv_b, rt.p(ws), ws.numel(), rt.stream()),
                 "hs_resblock_fwd")
         ctx.save_for_backward(x, y, saved, *params)
@@ -158,8 +115,9 @@ class ResBlockFn(Function):
         x, y, saved, *params = ctx.saved_tensors
         cfg = ctx.cfg
         dy = rt.as_cl(dy, cfg["dtype"])
-        grads = [_grad_like(t, ctx.needs_input_grad[2 + i]) for i, t in enumerate(params)]
-        d = ResBlockFn._desc(cfg, x.shape, params, grads)
+        d = ResBlockFn._desc(cfg, x.shape, params, forward=False)
+        grads = [_grad_like(t, n) for t, n in zip(params, ctx.needs_input_grad[2:])]
+        DL.set_grads(d, [rt.p(g) for g in grads])
         sv_b, ws_b = rt.query(_lib().hs_resblock_query, d)
         ws = rt.workspace(ws_b, x.device)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
@@ -235,37 +193,17 @@ class BertEmbedFn(Function):
         return None, None, dword, dpos, dtyp, dgamma, dbeta
 
 
-_BERT_LINS = ("q", "k", "v", "ao", "inter_l", "out_l")
-
-
 class BertLayerFn(Function):
-    """transformers BertLayer as one node.  params order:
-    q.w q.b k.w k.b v.w v.b ao.w ao.b ln1.g ln1.b inter.w inter.b out.w out.b ln2.g ln2.b"""
+    """transformers BertLayer as one node.  params: in the order of desc.BERT_LAYER_SLOTS"""
 
     @staticmethod
-    def _desc(cfg, x, mask, params, seed, grads=None):
+    def _desc(cfg, x, mask, params, seed):
         d = L.BertLayerDesc()
         B, Lq, H = x.shape
-        d.dtype = rt.hs_dtype(cfg["dtype"])
-        d.B, d.L, d.hidden, d.heads, d.inter = B, Lq, H, cfg["heads"], cfg["inter"]
-        d.ln_eps = cfg["eps"]
         tr = cfg["training"]
-        d.hidden_dropout = cfg["hidden_dropout"] if tr else 0.0
-        d.attn_dropout = cfg["attn_dropout"] if tr else 0.0
-        d.seed = seed
-        d.attention_mask = rt.p(mask)
-        g = grads if grads is not None else [None] * 16
-        I = cfg["inter"]
-        dims = {"q": (H, H), "k": (H, H), "v": (H, H), "ao": (H, H), "inter_l": (H, I), "out_l": (I, H)}
-        idx = {"q": 0, "k": 2, "v": 4, "ao": 6, "inter_l": 10, "out_l": 12}
-        for name in _BERT_LINS:
-            i = idx[name]
-            setattr(d, name, _lin(dims[name][0], dims[name][1], params[i], params[i + 1], g[i], g[i + 1]))
-        for name, i in (("ln1", 8), ("ln2", 14)):
-            n = L.Norm()
-            n.gamma, n.beta = rt.p(params[i]), rt.p(params[i + 1])
-            n.dgamma, n.dbeta = rt.p(g[i]), rt.p(g[i + 1])
-            setattr(d, name, n)
+        DL.fill_bert_layer(d, rt.hs_dtype(cfg["dtype"]), B, Lq, H, cfg["heads"], cfg["inter"], cfg["eps"],
+                          cfg["hidden_dropout"] if tr else 0.0, cfg["attn_dropout"] if tr else 0.0, params)
+        d.seed, d.attention_mask = seed, rt.p(mask)
         return d
 
     @staticmethod
@@ -294,8 +232,9 @@ class BertLayerFn(Function):
         dy = dy.contiguous()
         if dy.dtype != cfg["dtype"]:
             dy = dy.to(cfg["dtype"])
-        grads = [_grad_like(t, ctx.needs_input_grad[3 + i]) for i, t in enumerate(params)]
-        d = BertLayerFn._desc(cfg, x, mask, params, ctx.seed, grads)
+        d = BertLayerFn._desc(cfg, x, mask, params, ctx.seed)
+        grads = [_grad_like(t, n) for t, n in zip(params, ctx.needs_input_grad[3:])]
+        DL.set_grads(d, [rt.p(g) for g in grads])
         sv_b, ws_b = rt.query(_lib().hs_bert_layer_query, d)
         ws = rt.workspace(ws_b, x.device)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
@@ -335,7 +274,7 @@ class LinearFn(Function):
             if residual.dtype != out_dtype:
                 residual = residual.to(out_dtype)
         seed = rt.next_seed() if dropout_p > 0 else 0
-        lin = _lin(in_f, out_f, weight, bias)
+        lin = DL.linear(in_f, out_f, weight, bias)
         L.check(_lib().hs_linear_fwd(hdt, rt.p(x), M, in_f, C.byref(lin), rt.p(w_lp), rt.p(y), out_f, rt.hs_dtype(out_dtype),
                                      _ACT[act], rt.p(pre), rt.p(residual), out_f, dropout_p, seed, rt.stream()),
                 "hs_linear_fwd")
@@ -379,7 +318,7 @@ class LinearFn(Function):
         dw = _grad_like(weight, ctx.needs_input_grad[1])
         db = _grad_like(bias, bias is not None and ctx.needs_input_grad[2])
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        lin = _lin(in_f, out_f, weight, bias, dw, db)
+        lin = DL.linear(in_f, out_f, weight, bias, dw, db)
         wsb = _lib().hs_linear_bwd_ws_bytes(M, in_f, out_f, hdt)
         ws = rt.workspace(wsb, x.device)
         # the weight / bias gradient waits in the stream's deferred set when nothing reads it before the optimizer (rt)
@@ -413,7 +352,7 @@ class MlpGeluFn(Function):
         pre = torch.empty(x.shape[:-1] + (hid,), dtype=dt, device=x.device)
         h = torch.empty_like(pre)
         y = torch.empty(x.shape[:-1] + (out_f,), dtype=dt, device=x.device)
-        lin1, lin2 = _lin(in_f, hid, w1, b1), _lin(hid, out_f, w2, b2)
+        lin1, lin2 = DL.linear(in_f, hid, w1, b1), DL.linear(hid, out_f, w2, b2)
         L.check(_lib().hs_linear_fwd(hdt, rt.p(x), M, in_f, C.byref(lin1), rt.p(w1_lp), rt.p(h), hid, hdt, L.ACT_GELU,
                                      rt.p(pre), None, hid, 0.0, 0, rt.stream()), "hs_linear_fwd")
         L.check(_lib().hs_linear_fwd(hdt, rt.p(h), M, hid, C.byref(lin2), rt.p(w2_lp), rt.p(y), out_f, hdt, L.ACT_NONE,
@@ -437,8 +376,8 @@ class MlpGeluFn(Function):
         dw2, db2 = _grad_like(w2, need[3]), _grad_like(b2, b2 is not None and need[4])
         dpre = torch.empty_like(pre)                      # gradient wrt the hidden pre-activation
         dx = torch.empty_like(x) if need[0] else None
-        lin2 = _lin(hid, out_f, w2, b2, dw2, db2)
-        lin1 = _lin(in_f, hid, w1, b1, dw1, db1)
+        lin2 = DL.linear(hid, out_f, w2, b2, dw2, db2)
+        lin1 = DL.linear(in_f, hid, w1, b1, dw1, db1)
         # the two weight-gradient GEMMs run as one grouped grid (hs_wgrad_group_*): each call gets its own half of the workspace,
         # which stays alive until the group has been launched
         n2 = (int(_lib().hs_linear_bwd_ws_bytes(M, hid, out_f, hdt)) + 255) // 256 * 256
@@ -606,7 +545,7 @@ class MHAFn(Function):
         if packed and self_attn:
             # one GEMM: [B*L, E] x [3E, E]^T
             qkv = torch.empty((B, Lq, 3 * E), dtype=dt, device=dev)
-            lin = _lin(E, 3 * E, in_w, in_b)
+            lin = DL.linear(E, 3 * E, in_w, in_b)
             L.check(lib.hs_linear_fwd(hdt, rt.p(query), B * Lq, E, C.byref(lin), wlp("in"), rt.p(qkv), 3 * E, hdt, 0, None,
                                       None, 0, 0.0, 0, st), "hs_linear_fwd")
             q_t, k_t, v_t = qkv, qkv, qkv
@@ -616,20 +555,20 @@ class MHAFn(Function):
             q_t = torch.empty((B, Lq, E), dtype=dt, device=dev)
             kv = torch.empty((B, Lk, 2 * E), dtype=dt, device=dev)
             if packed:
-                lq = _lin(E, E, in_w, in_b)
+                lq = DL.linear(E, E, in_w, in_b)
                 L.check(lib.hs_linear_fwd(hdt, rt.p(query), B * Lq, E, C.byref(lq), wlp("in"), rt.p(q_t), E, hdt, 0, None, None,
                                           0, 0.0, 0, st), "hs_linear_fwd")
-                lkv = _lin(E, 2 * E, in_w, in_b, w_off=E * E, b_off=E)
+                lkv = DL.linear(E, 2 * E, in_w, in_b, w_off=E * E, b_off=E)
                 L.check(lib.hs_linear_fwd(hdt, rt.p(key), B * Lk, Ek, C.byref(lkv), wlp("in", E, E), rt.p(kv), 2 * E, hdt, 0,
                                           None, None, 0, 0.0, 0, st), "hs_linear_fwd")
             else:
-                lq = _lin(E, E, q_w, in_b)
+                lq = DL.linear(E, E, q_w, in_b)
                 L.check(lib.hs_linear_fwd(hdt, rt.p(query), B * Lq, E, C.byref(lq), wlp("q"), rt.p(q_t), E, hdt, 0, None, None,
                                           0, 0.0, 0, st), "hs_linear_fwd")
-                lk = _lin(Ek, E, k_w, in_b, b_off=E)
+                lk = DL.linear(Ek, E, k_w, in_b, b_off=E)
                 L.check(lib.hs_linear_fwd(hdt, rt.p(key), B * Lk, Ek, C.byref(lk), wlp("k"), rt.p(kv), 2 * E, hdt, 0, None,
                                           None, 0, 0.0, 0, st), "hs_linear_fwd")
-                lv = _lin(Ek, E, v_w, in_b, b_off=2 * E)
+                lv = DL.linear(Ek, E, v_w, in_b, b_off=2 * E)
                 L.check(lib.hs_linear_fwd(hdt, rt.p(key), B * Lk, Ek, C.byref(lv), wlp("v"), rt.p(kv, E * query.element_size()),
                                           2 * E, hdt, 0, None, None, 0, 0.0, 0, st), "hs_linear_fwd")
             k_t = v_t = kv
@@ -655,7 +594,7 @@ class MHAFn(Function):
         y = torch.empty((B, Lq, E), dtype=dt, device=dev)
         if residual is not None:
             residual = residual.contiguous()
-        lo = _lin(E, E, out_w, out_b)
+        lo = DL.linear(E, E, out_w, out_b)
         L.check(lib.hs_linear_fwd(hdt, rt.p(ctxv), B * Lq, E, C.byref(lo), wlp("out"), rt.p(y), E, hdt, 0, None,
                                   rt.p(residual), E, 0.0, 0, st), "hs_linear_fwd")
         keep = [t for t in (query, key if not self_attn else None, mask, q_t, k_t if k_t is not q_t else None, saved, ctxv)]
@@ -710,7 +649,7 @@ class MHAFn(Function):
 
         # output projection
         dctx = torch.empty_like(ctxv)
-        lo = _lin(E, E, out_w, out_b, d_out_w, d_out_b)
+        lo = DL.linear(E, E, out_w, out_b, d_out_w, d_out_b)
         run_lin_bwd(ctxv, B * Lq, E, lo, rt.p(lp_out), rt.p(dy), E, dctx, E)
         # attention core
         d = L.AttnDesc()
@@ -739,20 +678,20 @@ class MHAFn(Function):
             return rt.p(t, off_rows * cols * 2) if t is not None else None
 
         if packed and self_attn:
-            lin = _lin(E, 3 * E, in_w, in_b, d_in_w, d_in_b)
+            lin = DL.linear(E, 3 * E, in_w, in_b, d_in_w, d_in_b)
             run_lin_bwd(query, B * Lq, E, lin, lpp(lp_in), rt.p(dq_t), 3 * E, dquery, E)
         elif packed:
-            lq = _lin(E, E, in_w, in_b, d_in_w, d_in_b)
+            lq = DL.linear(E, E, in_w, in_b, d_in_w, d_in_b)
             run_lin_bwd(query, B * Lq, E, lq, lpp(lp_in), rt.p(dq_t), E, dquery, E)
-            lkv = _lin(E, 2 * E, in_w, in_b, d_in_w, d_in_b, w_off=E * E, b_off=E)
+            lkv = DL.linear(E, 2 * E, in_w, in_b, d_in_w, d_in_b, w_off=E * E, b_off=E)
             run_lin_bwd(key, B * Lk, Ek, lkv, lpp(lp_in, E, E), rt.p(dk_t), 2 * E, dkey, Ek)
         else:
-            lq = _lin(E, E, q_w, in_b, d_q_w, d_in_b)
+            lq = DL.linear(E, E, q_w, in_b, d_q_w, d_in_b)
             run_lin_bwd(query, B * Lq, E, lq, lpp(lp_q), rt.p(dq_t), E, dquery, E)
-            lk = _lin(Ek, E, k_w, in_b, d_k_w, d_in_b, b_off=E)
+            lk = DL.linear(Ek, E, k_w, in_b, d_k_w, d_in_b, b_off=E)
             run_lin_bwd(key, B * Lk, Ek, lk, lpp(lp_k), rt.p(dk_t), 2 * E, dkey, Ek)
             # v projection: dkey accumulates (k and v both read `key`)
-            lv = _lin(Ek, E, v_w, in_b, d_v_w, d_in_b, b_off=2 * E)
+            lv = DL.linear(Ek, E, v_w, in_b, d_v_w, d_in_b, b_off=2 * E)
             if dkey is not None:
                 dkey2 = torch.empty_like(dkey)
                 wsb = lib.hs_linear_bwd_ws_bytes(B * Lk, Ek, E, hdt)
@@ -827,7 +766,7 @@ class CrossAttnV2Fn(Function):
         vcat = torch.empty((B, 2, D), dtype=torch.float32, device=dev)
 
         def lin(inp, w, b, out, off, ld):
-            l_ = _lin(D, D, w, b)
+            l_ = DL.linear(D, D, w, b)
             L.check(lib.hs_linear_fwd(f32, rt.p(inp), B, D, C.byref(l_), None, rt.p(out, off * 4), ld, f32, 0, None, None, 0,
                                       0.0, 0, st), "hs_linear_fwd")
         lin(x, wQx, bQx, q, 0, D)
@@ -878,7 +817,7 @@ class CrossAttnV2Fn(Function):
         gKx, gbKx, gQx, gbQx, gVx, gbVx, gKy, gbKy, gVy, gbVy, gO, gbO = grads
 
         def lin_bwd(inp, w, b, dw, db, gout, off, ld, dx, res):
-            l_ = _lin(D, D, w, b, dw, db)
+            l_ = DL.linear(D, D, w, b, dw, db)
             wsb = lib.hs_linear_bwd_ws_bytes(B, D, D, f32)
             ws = rt.workspace(wsb, dev)
             L.check(lib.hs_linear_bwd(f32, rt.p(inp), B, D, C.byref(l_), None, rt.p(gout, off * 4), ld, rt.p(dx), D, f32,

@@ -14,6 +14,7 @@ import torch.nn as nn
 
 import hamspine
 
+from .. import desc as DL
 from .. import functional as F
 from .layers import Linear, LayerNorm
 
@@ -118,15 +119,10 @@ class BertLayer(nn.Module):
         self._inter = c.intermediate_size
 
     def forward(self, hidden_states, attention_mask=None):
-        a, so, o = self.attention.self, self.attention.output, self.output
+        a, so = self.attention.self, self.attention.output
         cfg = {"dtype": hamspine.compute_dtype(), "training": self.training, "heads": self._heads, "inter": self._inter,
                "eps": float(so.LayerNorm.eps), "hidden_dropout": float(so.dropout.p), "attn_dropout": float(a.dropout.p)}
-        return F.BertLayerFn.apply(
-            hidden_states, attention_mask, cfg,
-            a.query.weight, a.query.bias, a.key.weight, a.key.bias, a.value.weight, a.value.bias,
-            so.dense.weight, so.dense.bias, so.LayerNorm.weight, so.LayerNorm.bias,
-            self.intermediate.dense.weight, self.intermediate.dense.bias,
-            o.dense.weight, o.dense.bias, o.LayerNorm.weight, o.LayerNorm.bias)
+        return F.BertLayerFn.apply(hidden_states, attention_mask, cfg, *DL.bert_layer_params(self))
 
 
 class BertEncoder(nn.Module):

@@ -9,6 +9,7 @@ import torch.nn as nn
 
 import hamspine
 
+from .. import desc as DL
 from .. import functional as F
 from .layers import Linear
 
@@ -60,33 +61,19 @@ class BatchNormParams(nn.BatchNorm2d):
         raise RuntimeError("BatchNormParams is executed by its parent block (fused conv+BN node)")
 
 
-def _stage(conv, bn, training):
-    use_batch = training or not bn.track_running_stats
-    return {"geo": conv.geo(), "rm": bn.running_mean, "rv": bn.running_var, "bn": bn, "batch": use_batch}
-
-
 class _Block(nn.Module):
     def _pairs(self):
         raise NotImplementedError
 
     def forward(self, x):
-        pairs = self._pairs()
-        has_ds = self.downsample is not None
-        if has_ds:
-            pairs = pairs + [(self.downsample[0], self.downsample[1])]
+        pairs = DL.block_pairs(self)
         bn0 = pairs[0][1]
-        training = self.training
-        cfg = {
-            "dtype": hamspine.compute_dtype(), "training": training, "eps": bn0.eps,
-            "momentum": bn0.momentum if bn0.momentum is not None else 0.1,
-            "has_ds": has_ds, "stages": [_stage(c, b, training) for c, b in pairs],
-        }
-        params = []
-        for c, b in pairs:
-            params += [c.weight, b.weight, b.bias]
-            if training:
+        cfg = {"dtype": hamspine.compute_dtype(), "training": self.training, "eps": bn0.eps, "momentum": DL.bn_momentum(bn0),
+               "has_ds": self.downsample is not None, "stages": [(c.geo(), b.running_mean, b.running_var) for c, b in pairs]}
+        if self.training:
+            for _, b in pairs:
                 b.bump()
-        return F.ResBlockFn.apply(x, cfg, *params)
+        return F.ResBlockFn.apply(x, cfg, *[p for c, b in pairs for p in DL.conv_bn_params(c, b)])
 
 
 class BasicBlock(_Block):
@@ -126,11 +113,8 @@ class Bottleneck(_Block):
 
 
 def stem_forward(conv1, bn1, x, training):
-    cfg = {
-        "dtype": hamspine.compute_dtype(), "training": training, "eps": bn1.eps,
-        "momentum": bn1.momentum if bn1.momentum is not None else 0.1,
-        "running_mean": bn1.running_mean, "running_var": bn1.running_var,
-    }
+    cfg = {"dtype": hamspine.compute_dtype(), "training": training, "eps": bn1.eps, "momentum": DL.bn_momentum(bn1),
+           "running_mean": bn1.running_mean, "running_var": bn1.running_var}
     if training:
         bn1.bump()
     return F.StemFn.apply(x, conv1.weight, bn1.weight, bn1.bias, cfg)

@@ -21,6 +21,7 @@ from torch.nn.modules import module as _nn_module
 import hamspine
 
 from . import _lib as L
+from . import desc as DL
 from . import rt
 
 _CACHE_ATTR = "_hamspine_tower_cache"
@@ -52,7 +53,6 @@ def towers_enabled():
     gradient while the rest of the tower still runs; under torch's DistributedDataParallel (reference
     mibf_net/train_resnet.py:134) the tower's gradients become ready together at its end, which costs overlap, not
     correctness.  HAMSPINE_TOWER_EXEC=0 selects the per-block nodes."""
-    import os
     return os.environ.get("HAMSPINE_TOWER_EXEC", "1") != "0"
 
 
@@ -119,88 +119,74 @@ def _param_grad_ptrs(params, needs, device):
 # =====================================================================================================================
 # ResNet
 # =====================================================================================================================
-def _fill_cb(cb, conv, bn, dw=None, dg=None, db=None):
-    cb.Cin, cb.Cout, cb.R, cb.stride, cb.pad = conv.geo()
-    w = conv.weight
-    if not w.is_contiguous(memory_format=torch.channels_last):
-        raise L.HamspineError("hamspine.tower: conv filters must be channels_last (KRSC) in memory")
-    cb.w = w.data_ptr()
-    cb.gamma, cb.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
-    cb.running_mean = bn.running_mean.data_ptr() if bn.running_mean is not None else None
-    cb.running_var = bn.running_var.data_ptr() if bn.running_var is not None else None
-    cb.dw, cb.dgamma, cb.dbeta = dw, dg, db
-
-
 def resnet_blocks(model):
     return [b for layer in (model.layer1, model.layer2, model.layer3, model.layer4) for b in layer]
 
 
 def resnet_params(model):
     """stem (w, gamma, beta), then per block its main stages and the optional downsample pair, each (w, gamma, beta)"""
-    ps = [model.conv1.weight, model.bn1.weight, model.bn1.bias]
-    bns = [model.bn1]
-    for b in resnet_blocks(model):
-        pairs = b._pairs() + ([(b.downsample[0], b.downsample[1])] if b.downsample is not None else [])
-        for c, n in pairs:
-            ps += [c.weight, n.weight, n.bias]
-            bns.append(n)
-    return ps, bns
+    pairs = [(model.conv1, model.bn1)] + [cn for b in resnet_blocks(model) for cn in DL.block_pairs(b)]
+    return [p for c, n in pairs for p in DL.conv_bn_params(c, n)], [n for _, n in pairs]
 
 
-class _ResnetEntry:
-    def __init__(self, model, x_shape, dtype, training, inference, taps, params, needs, device):
-        blocks = resnet_blocks(model)
-        if len(blocks) > L.RESNET_MAX_BLOCKS:
-            raise L.HamspineError(f"hamspine.tower: {len(blocks)} residual blocks (max {L.RESNET_MAX_BLOCKS})")
-        self.store, gp, self.make_views = _param_grad_ptrs(params, needs, device)
-        self.grad_ptrs = gp
+bert_params = DL.bert_params      # the embeddings' parameters, then every layer's (desc.BERT_EMBED_SLOTS, BERT_LAYER_SLOTS)
+
+
+def _stage(conv, bn):
+    if not conv.weight.is_contiguous(memory_format=torch.channels_last):
+        raise L.HamspineError("hamspine.tower: conv filters must be channels_last (KRSC) in memory")
+    return (conv.geo(), *DL.conv_bn_params(conv, bn), bn.running_mean, bn.running_var)
+
+
+def resnet_desc(model, x_shape, dtype, training, inference, taps, grad_ptrs):
+    """hs_resnet_desc of `model` for one input shape and mode (no library call: the entry below asks for the plan)"""
+    blocks = resnet_blocks(model)
+    if len(blocks) > L.RESNET_MAX_BLOCKS:
+        raise L.HamspineError(f"hamspine.tower: {len(blocks)} residual blocks (max {L.RESNET_MAX_BLOCKS})")
+    d = L.ResnetDesc()
+    N, _, H, W = x_shape
+    hd = rt.hs_dtype(dtype)
+    eps, mom = model.bn1.eps, DL.bn_momentum(model.bn1)
+    DL.fill_stem(d.stem, hd, N, H, W, training, eps, mom, *_stage(model.conv1, model.bn1), inference=inference)
+    H, W = DL.stem_out(H), DL.stem_out(W)
+    d.n_blocks = len(blocks)
+    for i, b in enumerate(blocks):
+        stages = [_stage(c, n) for c, n in DL.block_pairs(b)]
+        if any(n.eps != eps or DL.bn_momentum(n) != mom for _, n in b._pairs()):
+            raise L.HamspineError("hamspine.tower: BatchNorm layers of a tower must share eps / momentum")
+        DL.fill_resblock(d.blocks[i], hd, N, H, W, training, eps, mom, stages, b.downsample is not None, inference=inference)
+        for _, _, R, stride, pad in (c.geo() for c, _ in b._pairs()):
+            H, W = DL.conv_out(H, R, stride, pad), DL.conv_out(W, R, stride, pad)
+    d.n_taps, d.tap_block[:len(taps)] = len(taps), taps
+    DL.set_grads(d, grad_ptrs)
+    return d
+
+
+class _Entry:
+    """what a tower keeps per (module, shape, mode): its descriptor, where its parameter gradients go, its arena sizes"""
+
+    def __init__(self, params, needs, device, dtype):
+        self.store, self.grad_ptrs, self.make_views = _param_grad_ptrs(params, needs, device)
         self.param_ptrs = [p.data_ptr() for p in params]
-        d = L.ResnetDesc()
-        N, _, H, W = x_shape
-        hd = rt.hs_dtype(dtype)
-        bn0 = model.bn1
-        eps, mom = bn0.eps, (bn0.momentum if bn0.momentum is not None else 0.1)
-        st = d.stem
-        st.dtype, st.N, st.H, st.W, st.training, st.eps, st.momentum, st.inference = hd, N, H, W, int(training), eps, mom, int(inference)
-        _fill_cb(st.cb, model.conv1, model.bn1, gp[0], gp[1], gp[2])
-        gi = 3
-        H, W = ((H + 6 - 7) // 2 + 1 + 2 - 3) // 2 + 1, ((W + 6 - 7) // 2 + 1 + 2 - 3) // 2 + 1
-        d.n_blocks = len(blocks)
-        for i, b in enumerate(blocks):
-            bd = d.blocks[i]
-            pairs = b._pairs()
-            bd.dtype, bd.N, bd.H, bd.W, bd.training, bd.eps, bd.momentum, bd.inference = hd, N, H, W, int(training), eps, mom, int(inference)
-            bd.n_main = len(pairs)
-            for j, (c, n) in enumerate(pairs):
-                if n.eps != eps or (n.momentum if n.momentum is not None else 0.1) != mom:
-                    raise L.HamspineError("hamspine.tower: BatchNorm layers of a tower must share eps / momentum")
-                _fill_cb(bd.main[j], c, n, gp[gi], gp[gi + 1], gp[gi + 2])
-                gi += 3
-                H = (H + 2 * c.padding[0] - c.kernel_size[0]) // c.stride[0] + 1
-                W = (W + 2 * c.padding[0] - c.kernel_size[0]) // c.stride[0] + 1
-            bd.has_ds = 1 if b.downsample is not None else 0
-            if b.downsample is not None:
-                _fill_cb(bd.ds, b.downsample[0], b.downsample[1], gp[gi], gp[gi + 1], gp[gi + 2])
-                gi += 3
-        d.n_taps = len(taps)
-        for t, bi in enumerate(taps):
-            d.tap_block[t] = bi
-        self.desc = d
-        self.plan = L.ResnetPlan()
-        L.check(L.lib().hs_resnet_query(C.byref(d), C.byref(self.plan)), "hs_resnet_query")
-        es = 2 if dtype == torch.bfloat16 else 4
-        self.taps = [(int(self.plan.tap_offset[t]), (N, int(self.plan.tap_H[t]), int(self.plan.tap_W[t]), int(self.plan.tap_C[t])), es)
-                     for t in range(len(taps))]
         self.dtype = dtype
         self.arena_version = rt.arena_version()
         self.outstanding = self.peak = 0
-        # bf16 shadows of the block convolutions' filters (the stem's filter is re-packed, not cast): rt.ensure_shadows
-        self.shadow_groups = [[params[i]] for i in range(3, len(params), 3)] if dtype == torch.bfloat16 else []
 
     def valid_for(self, params):
-        if self.arena_version != rt.arena_version():
-            return False
-        return all(p.data_ptr() == q for p, q in zip(params, self.param_ptrs))
+        return self.arena_version == rt.arena_version() and all(p.data_ptr() == q for p, q in zip(params, self.param_ptrs))
+
+
+class _ResnetEntry(_Entry):
+    def __init__(self, model, x_shape, dtype, training, inference, taps, params, needs, device):
+        super().__init__(params, needs, device, dtype)
+        self.desc = resnet_desc(model, x_shape, dtype, training, inference, taps, self.grad_ptrs)
+        self.plan = L.ResnetPlan()
+        L.check(L.lib().hs_resnet_query(C.byref(self.desc), C.byref(self.plan)), "hs_resnet_query")
+        self.saved_bytes, self.ws_bytes = int(self.plan.saved_bytes), int(self.plan.ws_bytes)
+        es = 2 if dtype == torch.bfloat16 else 4
+        self.taps = [(int(self.plan.tap_offset[t]), (x_shape[0], int(self.plan.tap_H[t]), int(self.plan.tap_W[t]), int(self.plan.tap_C[t])), es)
+                     for t in range(len(taps))]
+        self.shadow_groups = DL.resnet_shadow_groups(params) if dtype == torch.bfloat16 else []      # for rt.ensure_shadows
 
 
 class _Pending:
@@ -222,11 +208,6 @@ class _Pending:
     __del__ = finish
 
 
-def _forward_begins(ent, needs):
-    """a forward that will be backpropagated starts: count the forwards of this entry whose backward is still pending"""
-    return _Pending(ent) if any(needs) else None
-
-
 def _shared_buffer_unsafe(ent, params):
     """may this backward write into the entry's cached gradient buffer?  Not when the tower ran more than once in the graph
     being differentiated (gate / global-local models: reference model.py:257-281,334-337 -- autograd sums the gradients of
@@ -237,6 +218,42 @@ def _shared_buffer_unsafe(ent, params):
     if ent.peak > 1:
         return True
     return any(p.grad is not None and p.grad.data_ptr() == ent.store.ptr(i) for i, p in enumerate(params))
+
+
+def _tower_forward_begins(ctx, model, key, make_entry, params, needs, device):
+    """-> the cached entry of `key` (make_entry() builds a missing or outdated one), a fresh saved arena, the workspace"""
+    cache = model.__dict__.setdefault(_CACHE_ATTR, {})
+    ent = cache.get(key)
+    if ent is None or not ent.valid_for(params):
+        ent = cache[key] = make_entry()
+    rt.ensure_shadows(ent.shadow_groups)
+    saved = torch.empty(ent.saved_bytes, dtype=torch.uint8, device=device)
+    ctx.ent, ctx.saved_buf, ctx.params = ent, saved, params
+    ctx.counted = _Pending(ent) if any(needs) else None      # a forward that will be backpropagated: its backward is pending
+    return ent, saved, rt.workspace(ent.ws_bytes, device)
+
+
+def _tower_backward(ctx, n_lead, call):
+    """a tower node's backward: call(desc, saved, ws) makes its one C call; -> None for the n_lead leading inputs, then d(params)"""
+    ent, saved, params = ctx.ent, ctx.saved_buf, ctx.params
+    if saved is None:
+        raise RuntimeError("hamspine.tower: backward through a tower a second time: its saved activations are freed by the "
+                           "first backward (retain_graph=True is not supported on the tower nodes)")
+    _ = ctx.saved_tensors                        # raises if an output was modified in place since the forward
+    rt.wgrad_defer_flush_all()                   # the head path's deferred weight gradients: one grouped grid in front of the tower
+    desc, views = ent.desc, ent.make_views
+    if _shared_buffer_unsafe(ent, params):      # one-off private gradient buffers for this backward
+        store = _GradStore(params, tuple(ctx.needs_input_grad[n_lead:]), saved.device)
+        desc, views = DL.with_fresh_grads(ent.desc, store), store.views
+    ws = rt.workspace(ent.ws_bytes, saved.device)
+    if desc is ent.desc:
+        _with_milestones(ent, params, lambda: call(desc, saved, ws))
+    else:
+        call(desc, saved, ws)
+    ctx.saved_buf = None
+    if ctx.counted is not None:
+        ctx.counted.finish()
+    return (*[None] * n_lead, *views())
 
 
 class ResNetTowerFn(Function):
@@ -253,22 +270,13 @@ class ResNetTowerFn(Function):
         needs = tuple(ctx.needs_input_grad[2:])
         inference = not (training or any(needs))
         key = ("resnet", tuple(image.shape), dtype, training, inference, taps, needs)
-        cache = model.__dict__.setdefault(_CACHE_ATTR, {})
-        ent = cache.get(key)
-        if ent is None or not ent.valid_for(params):
-            ent = cache[key] = _ResnetEntry(model, image.shape, dtype, training, inference, taps, params, needs, image.device)
-        rt.ensure_shadows(ent.shadow_groups)
-        saved = torch.empty(int(ent.plan.saved_bytes), dtype=torch.uint8, device=image.device)
-        ws = rt.workspace(int(ent.plan.ws_bytes), image.device)
+        ent, saved, ws = _tower_forward_begins(
+            ctx, model, key, lambda: _ResnetEntry(model, image.shape, dtype, training, inference, taps, params, needs, image.device),
+            params, needs, image.device)
         L.check(L.lib().hs_resnet_fwd(C.byref(ent.desc), image.data_ptr(), saved.data_ptr(), saved.numel(), ws.data_ptr(),
                                       ws.numel(), rt.stream()), "hs_resnet_fwd")
-        outs = []
-        for off, (n, h, w, c), es in ent.taps:
-            t = saved[off:off + n * h * w * c * es].view(dtype).view(n, h, w, c).permute(0, 3, 1, 2)
-            outs.append(t)
-        ctx.ent, ctx.saved_buf = ent, saved
-        ctx.params = params
-        ctx.counted = _forward_begins(ent, needs)
+        outs = [saved[off:off + n * h * w * c * es].view(dtype).view(n, h, w, c).permute(0, 3, 1, 2)
+                for off, (n, h, w, c), es in ent.taps]
         if DEBUG_KEEP is not None:
             DEBUG_KEEP.append((ent, saved))
         # the outputs are views into the arena the backward reads (ReLU masks, BatchNorm inputs): registering them makes
@@ -278,58 +286,13 @@ class ResNetTowerFn(Function):
 
     @staticmethod
     def backward(ctx, *dys):
-        ent, saved, params = ctx.ent, ctx.saved_buf, ctx.params
-        if saved is None:
-            raise RuntimeError("hamspine.tower: backward through a tower a second time: its saved activations are freed by the "
-                               "first backward (retain_graph=True is not supported on the tower nodes)")
-        _ = ctx.saved_tensors                        # raises if an output was modified in place since the forward
-        rt.wgrad_defer_flush_all()                   # the head path's deferred weight gradients: one grouped grid in front of the tower
-        n = len(ent.taps)
-        ptrs = (C.c_void_p * n)()
-        keep = []
-        for t, dy in enumerate(dys):
-            if dy is None:
-                ptrs[t] = None
-                continue
-            dy = rt.as_cl(dy, ent.dtype)
-            keep.append(dy)
-            ptrs[t] = dy.data_ptr()
-        desc = ent.desc
-        views = ent.make_views
-        if _shared_buffer_unsafe(ent, params):      # one-off private gradient buffers for this backward
-            desc, views = _resnet_desc_with_fresh_grads(ent, params, tuple(ctx.needs_input_grad[2:]), saved.device)
-        ws = rt.workspace(int(ent.plan.ws_bytes), saved.device)
+        dys = [None if dy is None else rt.as_cl(dy, ctx.ent.dtype) for dy in dys]
+        ptrs = (C.c_void_p * len(dys))(*[None if dy is None else dy.data_ptr() for dy in dys])
 
-        def call():
+        def call(desc, saved, ws):
             L.check(L.lib().hs_resnet_bwd(C.byref(desc), ptrs, saved.data_ptr(), saved.numel(), ws.data_ptr(), ws.numel(),
                                           rt.stream()), "hs_resnet_bwd")
-        if desc is ent.desc:
-            _with_milestones(ent, params, call)
-        else:
-            call()
-        ctx.saved_buf = None
-        if ctx.counted is not None:
-            ctx.counted.finish()
-        return (None, None, *views())
-
-
-def _resnet_desc_with_fresh_grads(ent, params, needs, device):
-    store = _GradStore(params, needs, device)
-    d = L.ResnetDesc()
-    C.memmove(C.byref(d), C.byref(ent.desc), C.sizeof(L.ResnetDesc))
-    gi = 0
-
-    def put(cb):
-        nonlocal gi
-        cb.dw, cb.dgamma, cb.dbeta = store.ptr(gi), store.ptr(gi + 1), store.ptr(gi + 2)
-        gi += 3
-    put(d.stem.cb)
-    for i in range(d.n_blocks):
-        for j in range(d.blocks[i].n_main):
-            put(d.blocks[i].main[j])
-        if d.blocks[i].has_ds:
-            put(d.blocks[i].ds)
-    return d, store.views
+        return _tower_backward(ctx, 2, call)
 
 
 def resnet_taps(model, x, tap_layers):
@@ -347,93 +310,45 @@ def resnet_taps(model, x, tap_layers):
     if training:
         for bn in bns:
             bn.bump()
-    outs = ResNetTowerFn.apply(x, (model, taps, training), *params)
-    return outs
+    return ResNetTowerFn.apply(x, (model, taps, training), *params)
 
 
 # =====================================================================================================================
 # BERT
 # =====================================================================================================================
-def bert_params(model):
-    e = model.embeddings
-    ps = [e.word_embeddings.weight, e.position_embeddings.weight, e.token_type_embeddings.weight, e.LayerNorm.weight,
-          e.LayerNorm.bias]
-    for layer in model.encoder.layer:
-        a, so, o = layer.attention.self, layer.attention.output, layer.output
-        ps += [a.query.weight, a.query.bias, a.key.weight, a.key.bias, a.value.weight, a.value.bias,
-               so.dense.weight, so.dense.bias, so.LayerNorm.weight, so.LayerNorm.bias,
-               layer.intermediate.dense.weight, layer.intermediate.dense.bias,
-               o.dense.weight, o.dense.bias, o.LayerNorm.weight, o.LayerNorm.bias]
-    return ps
+def bert_desc(model, B, Lq, dtype, training, pack_rows, params, grad_ptrs):
+    """hs_bert_desc of `model` for one input shape and mode (no library call; seed is set per call)"""
+    layers = model.encoder.layer
+    if len(layers) > L.BERT_MAX_LAYERS:
+        raise L.HamspineError(f"hamspine.tower: {len(layers)} BertLayers (max {L.BERT_MAX_LAYERS})")
+    d = L.BertDesc()
+    hd = rt.hs_dtype(dtype)
+    e, H = model.embeddings, model.config.hidden_size
+    d.dtype, d.B, d.L, d.hidden = hd, B, Lq, H
+    d.vocab, d.max_pos, d.n_types = e.word_embeddings.weight.shape[0], e.position_embeddings.weight.shape[0], e.token_type_embeddings.weight.shape[0]
+    d.pad_id = -1 if e.word_embeddings.padding_idx is None else int(e.word_embeddings.padding_idx)
+    d.ln_eps, d.embed_dropout = float(e.LayerNorm.eps), float(e.dropout.p) if training else 0.0
+    DL.fill_bert_embeddings(d, params[:len(DL.BERT_EMBED_SLOTS)])
+    d.n_layers, d.pack_rows = len(layers), 1 if pack_rows else 0
+    for i, layer in enumerate(layers):
+        a, so = layer.attention.self, layer.attention.output
+        DL.fill_bert_layer(d.layers[i], hd, B, Lq, H, layer._heads, layer._inter, float(so.LayerNorm.eps),
+                          float(so.dropout.p) if training else 0.0, float(a.dropout.p) if training else 0.0,
+                          params[DL.bert_layer_slice(i)])
+    DL.set_grads(d, grad_ptrs)
+    return d
 
 
-def _lin(l, in_f, out_f, w, b, dw, db):
-    l.in_f, l.out_f = in_f, out_f
-    l.w, l.b, l.dw, l.db = w.data_ptr(), b.data_ptr(), dw, db
-
-
-class _BertEntry:
+class _BertEntry(_Entry):
     def __init__(self, model, B, Lq, dtype, training, params, needs, device, pack_rows=False):
-        c = model.config
-        if len(model.encoder.layer) > L.BERT_MAX_LAYERS:
-            raise L.HamspineError(f"hamspine.tower: {len(model.encoder.layer)} BertLayers (max {L.BERT_MAX_LAYERS})")
-        self.store, gp, self.make_views = _param_grad_ptrs(params, needs, device)
-        self.grad_ptrs = gp
-        self.param_ptrs = [p.data_ptr() for p in params]
-        d = L.BertDesc()
-        hd = rt.hs_dtype(dtype)
-        e = model.embeddings
-        H = c.hidden_size
-        d.dtype, d.B, d.L, d.hidden = hd, B, Lq, H
-        d.vocab, d.max_pos, d.n_types = e.word_embeddings.weight.shape[0], e.position_embeddings.weight.shape[0], e.token_type_embeddings.weight.shape[0]
-        d.pad_id = -1 if e.word_embeddings.padding_idx is None else int(e.word_embeddings.padding_idx)
-        d.ln_eps = float(e.LayerNorm.eps)
-        d.embed_dropout = float(e.dropout.p) if training else 0.0
-        d.word, d.pos, d.type0, d.gamma, d.beta = (p.data_ptr() for p in params[:5])
-        d.dword, d.dpos, d.dtype0, d.dgamma, d.dbeta = gp[:5]
-        d.n_layers = len(model.encoder.layer)
-        d.pack_rows = 1 if pack_rows else 0
+        super().__init__(params, needs, device, dtype)
         self.pack_rows = bool(pack_rows)
-        gi = 5
-        for i, layer in enumerate(model.encoder.layer):
-            ld = d.layers[i]
-            a, so, o = layer.attention.self, layer.attention.output, layer.output
-            I = layer._inter
-            ld.dtype, ld.B, ld.L, ld.hidden, ld.heads, ld.inter = hd, B, Lq, H, layer._heads, I
-            ld.ln_eps = float(so.LayerNorm.eps)
-            ld.hidden_dropout = float(so.dropout.p) if training else 0.0
-            ld.attn_dropout = float(a.dropout.p) if training else 0.0
-            p = params[gi:gi + 16]
-            g = gp[gi:gi + 16]
-            _lin(ld.q, H, H, p[0], p[1], g[0], g[1])
-            _lin(ld.k, H, H, p[2], p[3], g[2], g[3])
-            _lin(ld.v, H, H, p[4], p[5], g[4], g[5])
-            _lin(ld.ao, H, H, p[6], p[7], g[6], g[7])
-            ld.ln1.gamma, ld.ln1.beta, ld.ln1.dgamma, ld.ln1.dbeta = p[8].data_ptr(), p[9].data_ptr(), g[8], g[9]
-            _lin(ld.inter_l, H, I, p[10], p[11], g[10], g[11])
-            _lin(ld.out_l, I, H, p[12], p[13], g[12], g[13])
-            ld.ln2.gamma, ld.ln2.beta, ld.ln2.dgamma, ld.ln2.dbeta = p[14].data_ptr(), p[15].data_ptr(), g[14], g[15]
-            gi += 16
-        self.desc = d
+        self.desc = bert_desc(model, B, Lq, dtype, training, pack_rows, params, self.grad_ptrs)
         sv, ws, off = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        L.check(L.lib().hs_bert_query(C.byref(d), C.byref(sv), C.byref(ws), C.byref(off)), "hs_bert_query")
+        L.check(L.lib().hs_bert_query(C.byref(self.desc), C.byref(sv), C.byref(ws), C.byref(off)), "hs_bert_query")
         self.saved_bytes, self.ws_bytes, self.out_off = sv.value, ws.value, off.value
-        self.dtype = dtype
-        self.shape = (B, Lq, H)
-        self.arena_version = rt.arena_version()
-        self.outstanding = self.peak = 0
-        # bf16 shadows: q, k, v of a layer as the three segments of one buffer (read as the fused [3H][H] weight), the other
-        # three Linear weights on their own
-        self.shadow_groups = []
-        if dtype == torch.bfloat16:
-            for i in range(len(model.encoder.layer)):
-                b = 5 + 16 * i
-                self.shadow_groups += [[params[b], params[b + 2], params[b + 4]], [params[b + 6]], [params[b + 10]], [params[b + 12]]]
-
-    def valid_for(self, params):
-        if self.arena_version != rt.arena_version():
-            return False
-        return all(p.data_ptr() == q for p, q in zip(params, self.param_ptrs))
+        self.shape = (B, Lq, model.config.hidden_size)
+        self.shadow_groups = DL.bert_shadow_groups(params, len(model.encoder.layer)) if dtype == torch.bfloat16 else []
 
 
 class BertTowerFn(Function):
@@ -453,13 +368,9 @@ class BertTowerFn(Function):
         needs = tuple(ctx.needs_input_grad[3:])
         pack_rows = bool(pack_rows) and bert_pack_supported(model, B, Lq, dtype, mask, needs)
         key = ("bert", B, Lq, dtype, training, needs, pack_rows)
-        cache = model.__dict__.setdefault(_CACHE_ATTR, {})
-        ent = cache.get(key)
-        if ent is None or not ent.valid_for(params):
-            ent = cache[key] = _BertEntry(model, B, Lq, dtype, training, params, needs, ids.device, pack_rows)
-        rt.ensure_shadows(ent.shadow_groups)
-        saved = torch.empty(ent.saved_bytes, dtype=torch.uint8, device=ids.device)
-        ws = rt.workspace(ent.ws_bytes, ids.device)
+        ent, saved, ws = _tower_forward_begins(
+            ctx, model, key, lambda: _BertEntry(model, B, Lq, dtype, training, params, needs, ids.device, pack_rows),
+            params, needs, ids.device)
         seed = (rt.next_seed() * 64) & 0xFFFFFFFFFFFFFFFF if training else 0
         ent.desc.seed = seed
         L.check(L.lib().hs_bert_fwd(C.byref(ent.desc), ids.data_ptr(), rt.p(mask), saved.data_ptr(), saved.numel(),
@@ -467,57 +378,21 @@ class BertTowerFn(Function):
         Bq, Lq2, H = ent.shape
         es = 2 if dtype == torch.bfloat16 else 4
         out = saved[ent.out_off:ent.out_off + Bq * Lq2 * H * es].view(dtype).view(Bq, Lq2, H)
-        ctx.ent, ctx.saved_buf, ctx.seed = ent, saved, seed
-        ctx.ids, ctx.mask, ctx.params = ids, mask, params
-        ctx.counted = _forward_begins(ent, needs)
-        ctx.save_for_backward(out)                   # a view into the arena: in-place edits by a consumer are caught at backward
+        ctx.seed, ctx.ids, ctx.mask = seed, ids, mask
+        ctx.save_for_backward(out)                  # a view into the arena: in-place edits by a consumer are caught at backward
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        ent, saved, params = ctx.ent, ctx.saved_buf, ctx.params
-        if saved is None:
-            raise RuntimeError("hamspine.tower: backward through a tower a second time: its saved activations are freed by the "
-                               "first backward (retain_graph=True is not supported on the tower nodes)")
-        _ = ctx.saved_tensors
-        rt.wgrad_defer_flush_all()                   # (as the image tower's backward)
         dy = dy.contiguous()
-        if dy.dtype != ent.dtype:
-            dy = dy.to(ent.dtype)
-        desc, views = ent.desc, ent.make_views
-        if _shared_buffer_unsafe(ent, params):
-            desc, views = _bert_desc_with_fresh_grads(ent, params, tuple(ctx.needs_input_grad[3:]), saved.device)
-        desc.seed = ctx.seed
-        ws = rt.workspace(ent.ws_bytes, saved.device)
+        if dy.dtype != ctx.ent.dtype:
+            dy = dy.to(ctx.ent.dtype)
 
-        def call():
+        def call(desc, saved, ws):
+            desc.seed = ctx.seed
             L.check(L.lib().hs_bert_bwd(C.byref(desc), ctx.ids.data_ptr(), rt.p(ctx.mask), dy.data_ptr(), saved.data_ptr(),
                                         saved.numel(), ws.data_ptr(), ws.numel(), rt.stream()), "hs_bert_bwd")
-        if desc is ent.desc:
-            _with_milestones(ent, params, call)       # bert_params order: the backward finishes params[0] (embeddings) last
-        else:
-            call()
-        ctx.saved_buf = None
-        if ctx.counted is not None:
-            ctx.counted.finish()
-        return (None, None, None, *views())
-
-
-def _bert_desc_with_fresh_grads(ent, params, needs, device):
-    store = _GradStore(params, needs, device)
-    d = L.BertDesc()
-    C.memmove(C.byref(d), C.byref(ent.desc), C.sizeof(L.BertDesc))
-    d.dword, d.dpos, d.dtype0, d.dgamma, d.dbeta = (store.ptr(i) for i in range(5))
-    gi = 5
-    for i in range(d.n_layers):
-        ld = d.layers[i]
-        g = [store.ptr(gi + k) for k in range(16)]
-        ld.q.dw, ld.q.db, ld.k.dw, ld.k.db, ld.v.dw, ld.v.db, ld.ao.dw, ld.ao.db = g[:8]
-        ld.ln1.dgamma, ld.ln1.dbeta = g[8], g[9]
-        ld.inter_l.dw, ld.inter_l.db, ld.out_l.dw, ld.out_l.db = g[10:14]
-        ld.ln2.dgamma, ld.ln2.dbeta = g[14], g[15]
-        gi += 16
-    return d, store.views
+        return _tower_backward(ctx, 3, call)       # bert_params order: the backward finishes params[0] (embeddings) last
 
 
 def bert_pack_supported(model, B, Lq, dtype, mask, needs=None):
@@ -535,11 +410,8 @@ def bert_pack_supported(model, B, Lq, dtype, mask, needs=None):
     H = c.hidden_size
     if Lq > 128 or (B * Lq) % 8 != 0 or H % 8 != 0:
         return False
-    if needs is not None:
-        for i in range(len(model.encoder.layer)):
-            qkv = [bool(needs[5 + 16 * i + k]) for k in (0, 2, 4)]
-            if any(qkv) and not all(qkv):
-                return False
+    if needs is not None and not DL.qkv_trained_together(needs, len(model.encoder.layer)):
+        return False
     return all(H == 64 * layer._heads and layer._inter % 8 == 0 for layer in model.encoder.layer)
 
 
