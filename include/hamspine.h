@@ -1257,6 +1257,17 @@ hs_status hs_metrics_update_preds(const int64_t* preds, const int64_t* labels, i
    sklearn.metrics.roc_auc_score on host copies (mibf_net/predict_resnet_ham_image.py:103-110). */
 hs_status hs_metrics_auroc(const float* scores, const int32_t* labels, int64_t n, int64_t capacity, int32_t C, int64_t* counts,
                            void* stream);
+/* The counts of hs_metrics_auroc, integer for integer, in O(C n log n) instead of O(C n^2): per class the negatives' scores
+   are radix-sorted as order-preserving 32-bit keys (-0.0 == +0.0, denormals by value, NaN set aside: such a row counts in P or
+   Nn and takes part in no pair) and every positive finds its lower and upper bound among them.  Same arguments and limits as
+   hs_metrics_auroc; n == 0 zeroes counts and needs no workspace.  `workspace` is caller-owned device memory, 16-byte aligned;
+   hs_metrics_auroc_ranked_ws_bytes(n, C) (-1 outside the limits) holds all classes at once.  With less, but at least
+   ws_bytes(n, C) / C, the classes are taken in as many rounds as fit; with less than one class's share the call is refused
+   and nothing is written.  No read-back, no synchronisation.  Replaces, like hs_metrics_auroc, torchmetrics AUROC.compute
+   (pl_model_MOE2.py:170) and sklearn.metrics.roc_auc_score (mibf_net/predict_resnet_ham_image.py:103-110), which sort too. */
+int64_t hs_metrics_auroc_ranked_ws_bytes(int64_t n, int32_t C);
+hs_status hs_metrics_auroc_ranked(const float* scores, const int32_t* labels, int64_t n, int64_t capacity, int32_t C,
+                                  void* workspace, int64_t ws_bytes, int64_t* counts, void* stream);
 /* out: HS_METRICS_SCALARS + HS_METRICS_PER_CLASS * C doubles, laid out as above; every division in f64 from the integer counts,
    0 where a denominator is 0.  Macro averages run over the classes with tp + fp + fn > 0, the weighted ones use the supports.
    AUROC of a class is (2 less + eq) / (2 P Nn), NaN without a positive or without a negative; its macro average runs over the

@@ -6,7 +6,8 @@ What differs from the reference:
   * `Model4AAAI_MoE` derives from `pytorch_lightning.LightningModule` when that package imports, else from
     `hamspine.lightning_shim.LightningModule` (hyper-parameters, `log`, `.ckpt` save / load; no Trainer).
   * the three torchmetrics collections are ONE `hamspine.metrics.MulticlassMeter`: `validation_step` makes one kernel launch
-    and never synchronises, `on_validation_epoch_end` reads the device once.  The attributes `validation_macro_metrics`,
+    and never synchronises, `on_validation_epoch_end` reads the device once.  With torch.distributed initialised over more
+    than one rank the meter is made with group="world": every rank then logs the metrics of all ranks' rows.  The attributes `validation_macro_metrics`,
     `val_auroc` and `validation_per_class_metrics` all name that meter; like the reference's metric objects it adds no
     state-dict keys.  A class without positives has AUROC NaN and is left out of `val_AUROC` (torchmetrics: 0 with a warning).
   * the loss is `hamspine.functional.cross_entropy`, the optimizer `hamspine.optim.FusedAdam` (Adam with L2 weight decay, as
@@ -139,7 +140,11 @@ class Model4AAAI_MoE(_Base):
 
     def _meter_on(self, device):
         if self._meter is None or self._meter.device != device:
-            self._meter = MulticlassMeter(self.num_classes, device=device)
+            # under data parallelism every rank validates its own shard (hamspine.metrics.shard_indices) and logs the metrics
+            # of all ranks' rows; one process: the meter as it was
+            import torch.distributed as dist
+            many = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+            self._meter = MulticlassMeter(self.num_classes, device=device, group="world" if many else None)
         return self._meter
 
     def forward(self, x):

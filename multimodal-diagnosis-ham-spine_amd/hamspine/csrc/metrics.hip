@@ -5,6 +5,7 @@
 //   preds     the confusion-matrix half alone, from predicted labels
 //   auroc     per class, the pair counts of the Mann-Whitney statistic over the stored rows: an exact integer form of the area
 //             under the ROC curve
+//   ranked    the same counts from a radix sort of each class's negatives and a binary search per positive
 //   finalize  every ratio in f64 from the integer counts, in one block
 //
 // All state is integer counts (or stored f32 values that no later launch re-rounds), and the counts are added with integer
@@ -191,6 +192,186 @@ __global__ __launch_bounds__(kMetThreads) void metrics_auroc_kernel(const float*
     }
 }
 
+// ------------------------------------------------------------------------------------------------------ auroc, ranked
+// The same counts in O(C n log n) (DESIGN.md "Rank-based AUROC and metrics over all ranks").  Per class c every row gets a
+// 32-bit key: the order-preserving image of its score if the row is a NEGATIVE of c with a score that is not NaN, kRkNoKey
+// otherwise.  No score maps to kRkNoKey (+inf is 0xff800000), so after a sort of all n keys the negatives stand in front in
+// ascending order and whatever takes part in no pair stands behind them: the number of negatives need not be known, and a
+// positive's lower and upper bound among the n keys are its `less` and `less + eq`.  The sort is a least-significant-digit
+// radix sort, four passes of 8 bits, keys only: per pass a histogram per block of kRkTile keys, one exclusive scan per class
+// over (digit, block), and a stable scatter.  A workspace slot holds one class: two key buffers and the table of the scan;
+// the classes of one round are the grid's y.
+static constexpr int kRkItems = 8;                            // keys of one thread per tile
+static constexpr int kRkTile = kMetThreads * kRkItems;        // keys of one block: 2048
+static constexpr int kRkDigits = 256;                         // 8 bits per pass; one thread of a block per digit
+static constexpr int kRkSearch = 4;                           // rows of one thread of the search
+static constexpr unsigned kRkNoKey = 0xffffffffu;
+static_assert(kRkDigits == kMetThreads, "thread d of a block owns digit d");
+
+// order-preserving image of a score: -0.0 is +0.0, denormals keep their value, NaN is kRkNoKey (csrc/kan_grid.hip: key_of)
+__device__ __forceinline__ unsigned rank_key(float v) {
+    unsigned b = __float_as_uint(v);
+    if ((b & 0x7fffffffu) > 0x7f800000u) return kRkNoKey;
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+struct RankSlots {
+    unsigned* ws;                    // slot s: keys A [npad] | keys B [npad] | table [nblk][kRkDigits]
+    long long slot_words, npad;
+    int nblk, c0;                    // blocks per class; the class of slot 0
+};
+
+// key i of the pass's input: made from the stored row in the first pass, read from the other buffer afterwards
+__device__ __forceinline__ unsigned rank_load(const float* __restrict__ sc, const int* __restrict__ labels,
+                                              const unsigned* __restrict__ src, long long i, int c) {
+    if (src) return src[i];
+    const int y = labels[i];
+    return (y >= 0 && y != c) ? rank_key(sc[i]) : kRkNoKey;
+}
+
+// pass p reads A for odd p > 0 and B for even p > 0, and writes the other: 0 -> A, A -> B, B -> A, A -> B
+__device__ __forceinline__ const unsigned* rank_src(const unsigned* slot, long long npad, int pass) {
+    return pass == 0 ? nullptr : slot + ((pass & 1) ? 0 : npad);
+}
+
+__global__ __launch_bounds__(kMetThreads) void metrics_rank_hist_kernel(const float* __restrict__ scores,
+                                                                       const int* __restrict__ labels, long long n,
+                                                                       long long capacity, RankSlots rs, int pass) {
+    __shared__ unsigned s_h[kRkDigits];
+    const int c = rs.c0 + blockIdx.y;
+    unsigned* slot = rs.ws + (long long)blockIdx.y * rs.slot_words;
+    const unsigned* src = rank_src(slot, rs.npad, pass);
+    const float* sc = scores + (long long)c * capacity;
+    s_h[threadIdx.x] = 0;
+    __syncthreads();
+    const long long base = (long long)blockIdx.x * kRkTile + threadIdx.x;
+#pragma unroll
+    for (int it = 0; it < kRkItems; ++it) {
+        const long long i = base + it * kMetThreads;
+        if (i < n) atomicAdd(&s_h[(rank_load(sc, labels, src, i, c) >> (8 * pass)) & 255u], 1u);
+    }
+    __syncthreads();
+    slot[2 * rs.npad + (long long)blockIdx.x * kRkDigits + threadIdx.x] = s_h[threadIdx.x];
+}
+
+// table[b][d] <- the number of keys with a smaller digit, or with digit d in a block before b: where block b puts its first
+// key of digit d.  One block per class; thread d walks column d.
+__global__ __launch_bounds__(kMetThreads) void metrics_rank_scan_kernel(RankSlots rs) {
+    __shared__ unsigned s_t[kRkDigits];
+    unsigned* col = rs.ws + (long long)blockIdx.x * rs.slot_words + 2 * rs.npad + threadIdx.x;
+    unsigned tot = 0;
+#pragma unroll 8
+    for (int b = 0; b < rs.nblk; ++b) tot += col[(long long)b * kRkDigits];
+    s_t[threadIdx.x] = tot;
+    __syncthreads();
+    unsigned run = 0;
+    for (int d = 0; d < (int)threadIdx.x; ++d) run += s_t[d];
+    for (int b = 0; b < rs.nblk; ++b) {
+        const unsigned v = col[(long long)b * kRkDigits];
+        col[(long long)b * kRkDigits] = run;
+        run += v;
+    }
+}
+
+// Stable: a block takes its tile in kRkItems rounds of one key per thread, in row order; within a round a key goes behind the
+// keys of its digit in the waves before its own (s_w) and in the lanes before its own (the ballots).
+__global__ __launch_bounds__(kMetThreads) void metrics_rank_scatter_kernel(const float* __restrict__ scores,
+                                                                          const int* __restrict__ labels, long long n,
+                                                                          long long capacity, RankSlots rs, int pass) {
+    __shared__ unsigned s_base[kRkDigits];
+    __shared__ unsigned s_w[kMetThreads / 64][kRkDigits];
+    const int c = rs.c0 + blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned* slot = rs.ws + (long long)blockIdx.y * rs.slot_words;
+    const unsigned* src = rank_src(slot, rs.npad, pass);
+    unsigned* dst = slot + ((pass & 1) ? rs.npad : 0);
+    const float* sc = scores + (long long)c * capacity;
+    s_base[threadIdx.x] = slot[2 * rs.npad + (long long)blockIdx.x * kRkDigits + threadIdx.x];
+#pragma unroll
+    for (int w = 0; w < kMetThreads / 64; ++w) s_w[w][threadIdx.x] = 0;
+    __syncthreads();
+    const long long base = (long long)blockIdx.x * kRkTile + threadIdx.x;
+    for (int it = 0; it < kRkItems; ++it) {
+        const long long i = base + it * kMetThreads;
+        const bool live = i < n;
+        const unsigned key = live ? rank_load(sc, labels, src, i, c) : 0u;
+        const unsigned digit = (key >> (8 * pass)) & 255u;
+        unsigned long long peers = __ballot(live);             // the live lanes of this wave with this lane's digit
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (digit >> b) & 1u;
+            const unsigned long long m = __ballot(live && bit);
+            peers &= bit ? m : ~m;
+        }
+        const unsigned long long before = peers & ((1ull << lane) - 1ull);
+        if (live && before == 0) s_w[wv][digit] = (unsigned)__popcll(peers);
+        __syncthreads();
+        if (live) {
+            unsigned at = s_base[digit] + (unsigned)__popcll(before);
+            for (int w = 0; w < wv; ++w) at += s_w[w][digit];
+            if (at < n) dst[at] = key;                         // always, if the table is this pass's; a bound all the same
+        }
+        __syncthreads();
+        unsigned add = 0;
+#pragma unroll
+        for (int w = 0; w < kMetThreads / 64; ++w) {
+            add += s_w[w][threadIdx.x];
+            s_w[w][threadIdx.x] = 0;
+        }
+        s_base[threadIdx.x] += add;
+        __syncthreads();
+    }
+}
+
+// every positive with a score looks its key up among the sorted keys (buffer B after four passes); P and Nn count NaN rows too
+__global__ __launch_bounds__(kMetThreads) void metrics_rank_search_kernel(const float* __restrict__ scores,
+                                                                         const int* __restrict__ labels, long long n,
+                                                                         long long capacity, RankSlots rs,
+                                                                         long long* __restrict__ counts) {
+    __shared__ unsigned long long s_red[kMetThreads / 64];
+    const int c = rs.c0 + blockIdx.y;
+    const unsigned* sorted = rs.ws + (long long)blockIdx.y * rs.slot_words + rs.npad;
+    const float* sc = scores + (long long)c * capacity;
+    unsigned pos = 0, neg = 0;
+    unsigned long long less = 0, eq = 0;                       // kRkSearch counts below 2^31 each
+#pragma unroll
+    for (int u = 0; u < kRkSearch; ++u) {
+        const long long i = ((long long)blockIdx.x * kRkSearch + u) * kMetThreads + threadIdx.x;
+        const int y = i < n ? labels[i] : -1;
+        pos += y == c;
+        neg += y >= 0 && y != c;
+        const unsigned k = y == c ? rank_key(sc[i]) : kRkNoKey;
+        if (k == kRkNoKey) continue;
+        unsigned lo = 0, hi = (unsigned)n;
+        while (lo < hi) {
+            const unsigned mid = lo + ((hi - lo) >> 1);
+            if (sorted[mid] < k) lo = mid + 1;
+            else hi = mid;
+        }
+        const unsigned lower = lo;
+        hi = (unsigned)n;
+        while (lo < hi) {
+            const unsigned mid = lo + ((hi - lo) >> 1);
+            if (sorted[mid] <= k) lo = mid + 1;
+            else hi = mid;
+        }
+        less += lower;
+        eq += lo - lower;
+    }
+    const unsigned long long P = block_sum(pos, s_red), Nn = block_sum(neg, s_red);
+    const unsigned long long l = block_sum((unsigned)less, s_red) + (block_sum((unsigned)(less >> 32), s_red) << 32);
+    const unsigned long long e = block_sum((unsigned)eq, s_red) + (block_sum((unsigned)(eq >> 32), s_red) << 32);
+    if (threadIdx.x == 0) {
+        add_i64(counts + c * 4 + 0, l);
+        add_i64(counts + c * 4 + 1, e);
+        add_i64(counts + c * 4 + 2, P);
+        add_i64(counts + c * 4 + 3, Nn);
+    }
+}
+
+static long long rank_npad(long long n) { return (n + 3) & ~3ll; }
+static long long rank_slot_words(long long n) { return n ? 2 * rank_npad(n) + (long long)ceil_div(n, kRkTile) * kRkDigits : 0; }
+
 // ----------------------------------------------------------------------------------------------------------- finalize
 // Replaces the torchmetrics .compute() calls of pl_model_MOE2.py:169-171 and the sklearn calls of ConNexT/models/test.py:
 // 112-130, scripts/train.py:121-129.  One wave; lane c owns class c, lane 0 adds the averages up in class order.
@@ -322,6 +503,51 @@ hs_status hs_metrics_auroc(const float* scores, const int32_t* labels, int64_t n
     spans = ceil_div(n, jspan);
     metrics_auroc_kernel<<<dim3(itiles, C, spans), kMetThreads, 0, st>>>(scores, labels, n, capacity, jspan, (long long*)counts);
     HS_LAUNCH_CHECK();
+    return HS_OK;
+}
+
+int64_t hs_metrics_auroc_ranked_ws_bytes(int64_t n, int32_t C) {
+    if (!metrics_classes_ok(C) || n < 0 || n >= (1ll << 31)) return -1;
+    return (int64_t)C * rank_slot_words(n) * 4;
+}
+
+hs_status hs_metrics_auroc_ranked(const float* scores, const int32_t* labels, int64_t n, int64_t capacity, int32_t C,
+                                  void* workspace, int64_t ws_bytes, int64_t* counts, void* stream) {
+    HS_REQUIRE(metrics_classes_ok(C), "hs_metrics_auroc_ranked: %d classes, supported 2..%d", C, kMetMaxC);
+    HS_REQUIRE(scores && labels && counts, "hs_metrics_auroc_ranked: null pointer");
+    HS_REQUIRE(n >= 0 && n <= capacity && capacity < (1ll << 31), "hs_metrics_auroc_ranked: %lld rows, capacity %lld",
+               (long long)n, (long long)capacity);
+    const long long slot_words = rank_slot_words(n);
+    if (n > 0) {
+        HS_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "hs_metrics_auroc_ranked: workspace is null or not 16-byte aligned");
+        HS_REQUIRE(ws_bytes >= slot_words * 4, "hs_metrics_auroc_ranked: workspace of %lld bytes, one class of %lld rows takes %lld",
+                   (long long)ws_bytes, (long long)n, slot_words * 4);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HS_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)C * 4 * sizeof(int64_t), st));
+    if (n == 0) return HS_OK;
+    const long long fit = ws_bytes / (slot_words * 4);
+    const int per_round = fit < C ? (int)fit : C;              // classes sorted side by side
+    RankSlots rs;
+    rs.ws = (unsigned*)workspace;
+    rs.slot_words = slot_words;
+    rs.npad = rank_npad(n);
+    rs.nblk = ceil_div(n, kRkTile);
+    for (int c0 = 0; c0 < C; c0 += per_round) {
+        const int cls = C - c0 < per_round ? C - c0 : per_round;
+        rs.c0 = c0;
+        for (int pass = 0; pass < 4; ++pass) {
+            metrics_rank_hist_kernel<<<dim3(rs.nblk, cls), kMetThreads, 0, st>>>(scores, labels, n, capacity, rs, pass);
+            HS_LAUNCH_CHECK();
+            metrics_rank_scan_kernel<<<cls, kMetThreads, 0, st>>>(rs);
+            HS_LAUNCH_CHECK();
+            metrics_rank_scatter_kernel<<<dim3(rs.nblk, cls), kMetThreads, 0, st>>>(scores, labels, n, capacity, rs, pass);
+            HS_LAUNCH_CHECK();
+        }
+        metrics_rank_search_kernel<<<dim3(ceil_div(n, kRkSearch * kMetThreads), cls), kMetThreads, 0, st>>>(
+            scores, labels, n, capacity, rs, (long long*)counts);
+        HS_LAUNCH_CHECK();
+    }
     return HS_OK;
 }
 

@@ -14,6 +14,12 @@ process, alternating, `--rounds` times after a warm-up round; every figure is th
   baseline  host clock per batch of the two `.cpu()` copies, and around the scikit-learn calls at the end
 The last line is the forward pass of one validation batch of the flagship model (bench.py's C2, batch 32, no_grad) in the same
 process, the yardstick for the pair count.
+
+    python tools/metrics_bench.py --ranked 2003x7,10000x7,50000x7,200000x7,1000000x7 --out profiles/metrics_ranked.txt
+
+times compute() of two meters holding the same rows, auroc="pairs" and auroc="ranked", alternating, and names the smallest
+measured row count from which the ranked route is faster by more than the spread (max - min over the rounds) of either route:
+the value for hamspine.metrics.AUTO_RANKED_ROWS.
 """
 import argparse
 import os
@@ -102,8 +108,71 @@ def c2_forward_ms(iters, warmup):
     return (time.perf_counter() - t0) / iters * 1e3
 
 
+def ranked_lines(shapes, rounds):
+    """compute() with auroc="pairs" against auroc="ranked" on the same stored rows"""
+    from hamspine import metrics as M
+    lines = [f"metrics_bench --ranked: MulticlassMeter.compute() on stored rows, auroc=\"pairs\" (hs_metrics_auroc) against "
+             f"auroc=\"ranked\" (hs_metrics_auroc_ranked), one process, alternating; median of {rounds} rounds after one warm-up "
+             "round (min, max); host clock around compute(), device events around the count launches alone",
+             f"{'rows':>9} {'C':>3}  {'pairs compute()':>44}  {'ranked compute()':>44}  {'pairs count, device':>20}  "
+             f"{'ranked count, device':>20}  ranked workspace"]
+    threshold = None
+    for shape in shapes.split(","):
+        N, C = (int(v) for v in shape.split("x"))
+        g = torch.Generator().manual_seed(N + C)
+        labels = torch.randint(0, C, (N,), generator=g)
+        logits = torch.randn(N, C, generator=g)
+        logits[torch.arange(N), labels] += 1.0
+        logits, labels = logits.cuda(), labels.cuda()
+        cap = 4096
+        while cap < N:
+            cap *= 2
+        meters = {k: M.MulticlassMeter(C, capacity=cap, auroc=k) for k in ("pairs", "ranked")}
+        for m in meters.values():
+            for at in range(0, N, 65536):
+                m.update(logits[at:at + 65536], labels[at:at + 65536])
+        host, dev, res = {k: [] for k in meters}, {k: [] for k in meters}, {}
+        scratch = torch.zeros((C, 4), dtype=torch.int64, device="cuda")
+        for r in range(rounds + 1):
+            for k, m in meters.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res[k] = m.compute()
+                dt = time.perf_counter() - t0
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ev[0].record()
+                if k == "pairs":
+                    M.metrics_auroc(m.scores, m.labels, m.n, scratch)
+                else:
+                    M.metrics_auroc_ranked(m.scores, m.labels, m.n, scratch, m._workspace(m.n))
+                ev[1].record()
+                torch.cuda.synchronize()
+                if r:
+                    host[k].append(dt * 1e3)
+                    dev[k].append(ev[0].elapsed_time(ev[1]))
+        assert np.array_equal(meters["pairs"].auroc_counts(), meters["ranked"].auroc_counts()), "the two routes count differently"
+        for k, v in res["pairs"].items():
+            assert np.array_equal(res["ranked"][k], v, equal_nan=True), k
+        med = {k: statistics.median(v) for k, v in host.items()}
+        spread = max(max(v) - min(v) for v in host.values())
+        faster = med["pairs"] - med["ranked"] > spread
+        if faster and threshold is None:
+            threshold = N
+        if not faster:
+            threshold = None                                  # the ranked route has to stay ahead from the threshold on
+        lines.append(f"{N:>9} {C:>3}  {_fmt(host['pairs']):>44}  {_fmt(host['ranked']):>44}  "
+                     f"{statistics.median(dev['pairs']) * 1e3:>17.1f} us  {statistics.median(dev['ranked']) * 1e3:>17.1f} us  "
+                     f"{M.auroc_ranked_ws_bytes(cap, C) / 2 ** 20:.2f} MiB   spread {spread * 1e3:.1f} us, ranked "
+                     f"{'faster by more' if faster else 'not faster by more'}")
+    lines.append(f"AUTO_RANKED_ROWS = {threshold}: the smallest measured row count from which the ranked route is faster by more than "
+                 "the spread of either route (None: at no measured size)")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ranked", default=None, metavar="SHAPES", help="time auroc='pairs' against auroc='ranked' at these "
+                    "rows x classes instead of the validation pass, e.g. 2003x7,50000x7")
     ap.add_argument("--shapes", default="2003x7,50000x7")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--forward-iters", type=int, default=30, help="C2 forward passes timed (0 skips that leg)")
@@ -114,9 +183,13 @@ def main():
     from hamspine.metrics import MulticlassMeter
     hamspine.require_device()
     hamspine.set_compute_dtype("bf16")
-    lines = [f"metrics_bench: validation pass in batches of {BATCH}, f32 logits on the device; median of {args.rounds} alternating "
-             "rounds after one warm-up round (min, max)"]
-    for shape in args.shapes.split(","):
+    if args.ranked:
+        lines = ranked_lines(args.ranked, args.rounds)
+        args.shapes, args.forward_iters = "", 0
+    else:
+        lines = [f"metrics_bench: validation pass in batches of {BATCH}, f32 logits on the device; median of {args.rounds} alternating "
+                 "rounds after one warm-up round (min, max)"]
+    for shape in filter(None, args.shapes.split(",")):
         N, C = (int(v) for v in shape.split("x"))
         g = torch.Generator().manual_seed(N + C)
         labels = torch.randint(0, C, (N,), generator=g)
